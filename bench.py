@@ -10,9 +10,16 @@ quantity the reference's benchmark scales with); ``ms_per_step`` the wall time o
 
 Run: ``python bench.py`` (1 GPU), ``python bench.py --gpus N`` (starts N rank processes itself) or
 ``torchrun --nproc-per-node N bench.py --gpus N`` (WORLD_SIZE must equal ``--gpus``).
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line.
+``--dump-outputs DIR`` also writes what the last timed step computed (rank 0's local arrays) as
+``DIR/<name>.npy``; the inputs are seeded, so two builds can be compared output for output.
+``--full`` adds everything that is not needed for the headline figure, after the timed loop: the
+fp64 self-checks of the timed path (``extra``), the exact fp32-MFMA side-by-side
+(``--exact-steps``), the reference-style iteration (``--with-reference``), the number of ranks a
+device all-reduce reaches and, at world > 1, the k-means all-reduce payload timed on every path
+(``extra.comm_ab``).
 ``--comm {pg,native,ipc}`` picks the device collective path of the timed loop, ``--ring
-{ring,direct}`` the Y-block circulation; at world > 1 the k-means all-reduce payload is also timed
-on every path (``extra.comm_ab``) and ``extra.comm.collective_paths`` counts the path each
+{ring,direct}`` the Y-block circulation; ``extra.comm.collective_paths`` counts the path each
 collective of the run took.
 Secondary workloads: ``--workload cdist`` (distance_matrix, streamed), ``--workload knn`` (the
 distance_matrix config reduced to each row's ``--topk`` nearest rows by the fused kernel, no
@@ -45,20 +52,31 @@ def parse():
     p.add_argument("--precision", default="fast", choices=["fast", "exact"],
                    help="kmeans: 'fast' = distances by a 3-term fp16 split on the matrix cores (fp32-GEMM "
                         "accuracy, checked against fp64 in tests/test_gpu_kernels.py); 'exact' = fp32-input MFMA")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed loop also run the self-checks against fp64 and the secondary measurements "
+                        "(--exact-steps, --with-reference, --comm-ab); a plain run only times the steps")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step computed (rank 0's local arrays) as DIR/<name>.npy, float32 "
+                        "or float64, at most 60 MB in all (a fixed, seeded sample of a larger array)")
     p.add_argument("--exact-steps", type=int, default=5,
-                   help="kmeans fast: also time this many steps of the exact fp32-MFMA path (0 = skip)")
+                   help="--full, kmeans fast: also time this many steps of the exact fp32-MFMA path (0 = skip)")
     p.add_argument("--with-reference", action="store_true",
-                   help="also time a reference-style (heat 1.1 algorithm) iteration on torch-ROCm")
+                   help="--full: also time a reference-style (heat 1.1 algorithm) iteration on torch-ROCm")
     p.add_argument("--comm", default="pg", choices=["pg", "native", "ipc"],
                    help="device collectives of the timed loop: torch ProcessGroupNCCL (RCCL), the native "
                         "stream-ordered RCCL communicator (comm.hip) or the xGMI IPC kernels (ipc_allreduce.hip)")
     p.add_argument("--ring", default="ring", choices=["ring", "direct"],
                    help="Y-block circulation of the cdist/knn workloads: neighbour ring or all-peer direct posts")
     p.add_argument("--comm-ab", type=int, default=1,
-                   help="world > 1: also time the k-means all-reduce payload on every comm path after the timed "
-                        "loop (0 = skip), in a separate child job so a failing path cannot cost the result")
+                   help="--full, world > 1: also time the k-means all-reduce payload on every comm path after the "
+                        "timed loop (0 = skip), in a separate child job so a failing path cannot cost the result")
     p.add_argument("--comm-ab-child", default=None, help=argparse.SUPPRESS)
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if args.with_reference and not args.full:
+        p.error("--with-reference is one of the --full measurements: add --full")
+    return args
 
 
 def _free_port() -> int:
@@ -193,7 +211,7 @@ def main():
             torch.cuda.synchronize()
 
     n_gpus = comm.size
-    extra = {"world_size_seen_by_rccl": rccl_world_size(comm)}
+    extra = {"world_size_seen_by_rccl": rccl_world_size(comm)} if args.full else {}
     scaling = "weak"
     if args.workload == "kmeans":
         # 1.25e7 points per GPU (8 GPUs = the BASELINE's 1e8); a CPU-only host (the gloo contract
@@ -209,11 +227,14 @@ def main():
         sync()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            km.step(x)
+            shift = km.step(x)
         sync()
         dt = time.perf_counter() - t0
         # slowest rank defines the step
         ms = rank_times(comm, dt, args.steps, extra)
+        # written before anything else runs: later steps may reuse the kernels' buffers
+        dump_outputs(args, comm, {"cluster_centers": km.cluster_centers_.larray, "labels": km._last_labels,
+                                  "centroid_shift": torch.as_tensor(shift)})
         flops = 2.0 * n * k * f
         value = flops / (ms * 1e-3) / 1e9
         metric = "kmeans_iter_gflops"
@@ -229,7 +250,7 @@ def main():
                               "not an fp32-MFMA rate" if args.precision == "fast"
                               else "fp32-input MFMA (exact fp32 products)")
         extra["tflops_per_gpu"] = value / n_gpus / 1e3
-        if args.precision == "fast" and args.exact_steps > 0:
+        if args.full and args.precision == "fast" and args.exact_steps > 0:
             # the exact fp32-MFMA path on the same data, for an honest side-by-side
             km_exact = ht.cluster.KMeans(n_clusters=k, init="random", max_iter=1, tol=None, random_state=42)
             km_exact.precision = "exact"
@@ -244,7 +265,8 @@ def main():
             dte = comm.allreduce(dte, ht.MPI.MAX) if comm.size > 1 else dte
             extra["exact_ms_per_step"] = dte / args.exact_steps * 1e3
             extra["exact_gflops_fp32"] = flops / (extra["exact_ms_per_step"] * 1e-3) / 1e9
-        extra.update(validate_kmeans(km, x, comm, k))
+        if args.full:
+            extra.update(validate_kmeans(km, x, comm, k))
         if args.with_reference:
             extra["reference_impl_ms"] = reference_iteration(x, km, k)
             extra["speedup_vs_reference_impl"] = extra["reference_impl_ms"] / ms
@@ -257,9 +279,11 @@ def main():
         ht.random.seed(7)
         x = ht.random.rand(n, f, split=0, device=dev)
         tiles = [0]
+        last = {}
 
         def consume(d, i, j):
             tiles[0] += 1
+            last["tile"], last["at"] = d, (i, j)   # a view of the reused tile buffer, no copy
 
         def one():
             ht.spatial.cdist_stream(x, x, consume, tile=65536)
@@ -273,13 +297,17 @@ def main():
         sync()
         dt = time.perf_counter() - t0
         ms = rank_times(comm, dt, args.steps, extra)
+        if last:   # the tile the last step produced last (the buffer still holds it) and its global offsets
+            dump_outputs(args, comm, {"last_tile": last["tile"],
+                                      "last_tile_offsets": torch.tensor(last["at"], dtype=torch.float64)})
         value = 2.0 * n * n * f / (ms * 1e-3) / 1e9
         metric, unit = "cdist_gflops", "GFLOP/s"
         cfg = {"model": "cdist euclidean n={} f={} float32 split=0 (streamed tiles)".format(n, f),
                "global_batch": n, "seq_len": f, "parallelism": "dp{}".format(n_gpus)}
         extra["flop_convention"] = "2*n*n*f (the distance GEMM of the quadratic expansion)"
         extra["distances_per_s"] = n * n / (ms * 1e-3)
-        extra.update(validate_cdist(x, comm))
+        if args.full:
+            extra.update(validate_cdist(x, comm))
         scaling = "strong"
     elif args.workload == "knn":
         # the same 1e6 x 128 self-distance problem, each row reduced to its topk nearest rows by the
@@ -296,6 +324,7 @@ def main():
         sync()
         dt = time.perf_counter() - t0
         ms = rank_times(comm, dt, args.steps, extra)
+        dump_outputs(args, comm, {"distances": d.larray, "indices": idx.larray})
         value = 2.0 * n * n * f / (ms * 1e-3) / 1e9
         metric, unit = "knn_gflops", "GFLOP/s (fp32-equivalent)"
         cfg = {"model": "cdist_topk euclidean n={} f={} k={} float32 split=0".format(n, f, args.topk),
@@ -306,7 +335,8 @@ def main():
         st = _k._KNN_STATS
         extra["certified_queries"] = st["queries"]
         extra["certified_rechecked_fraction"] = st["rechecked"] / st["queries"] if st["queries"] else None
-        extra.update(validate_knn(x, d, idx, comm))
+        if args.full:
+            extra.update(validate_knn(x, d, idx, comm))
         scaling = "strong"
     elif args.workload == "qr":
         # BASELINE tall-skinny QR config: 1e7 x 4096 float32 split=0 on 8 GPUs = 1.25e6 rows per GPU
@@ -331,16 +361,19 @@ def main():
         sync()
         dt = time.perf_counter() - t0
         ms = rank_times(comm, dt, args.steps, extra)
+        dump_outputs(args, comm, {"q": q.larray, "r": r.larray})
         flops = 4.0 * n * f * f - 4.0 * f ** 3 / 3
         value = flops / (ms * 1e-3) / 1e9
         metric, unit = "tsqr_gflops", "GFLOP/s"
         cfg = {"model": "tsqr Q,R m={} n={} float32 split=0 (CholeskyQR2)".format(n, f), "global_batch": n,
                "seq_len": f, "parallelism": "dp{}".format(n_gpus), "n_per_gpu": args.n_per_gpu}
         extra["flop_convention"] = "4 m n^2 - 4 n^3 / 3 (Householder QR with Q formed)"
-        extra.update(validate_qr(a, q, r, comm))
+        if args.full:
+            extra.update(validate_qr(a, q, r, comm))
     else:
         args.n_per_gpu = args.n_per_gpu or 1_000_000_000
         n = args.n_per_gpu * n_gpus
+        ht.random.seed(5)
         x = ht.random.rand(n, split=0, device=dev)
         for _ in range(args.warmup):
             ht.mean(x), ht.var(x)
@@ -352,9 +385,11 @@ def main():
         sync()
         dt = time.perf_counter() - t0
         ms = rank_times(comm, dt, args.steps, extra)
+        dump_outputs(args, comm, {"mean": m.larray, "var": v.larray})
         value = 2 * n * 4 / (ms * 1e-3) / 1e9
         metric, unit = "moments_GB_per_s", "GB/s"
-        extra.update(validate_moments(x, m, v, comm))
+        if args.full:
+            extra.update(validate_moments(x, m, v, comm))
         cfg = {"model": "mean+var float32 split=0", "global_batch": n, "seq_len": 1,
                "parallelism": "dp{}".format(n_gpus)}
     if args.workload == "kmeans" and args.precision == "fast":
@@ -373,7 +408,7 @@ def main():
            "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True, "scaling": scaling,
            "vs_baseline": None, "dtype": "fp32", "data": "synthetic (device Threefry normal samples)",
            "config": cfg, "extra": extra}
-    if comm.size > 1 and args.comm_ab:
+    if args.full and comm.size > 1 and args.comm_ab:
         # after the timed loop and its result: the all-reduce of the k-means payload on every
         # path, in a SEPARATE job (one child per rank, its own rendezvous): a path that crashes or
         # hangs on this node costs that record, never the measurement above
@@ -381,6 +416,40 @@ def main():
         extra["comm_ab"] = comm_ab_isolated(comm, [8, payload])
     if comm.rank == 0:
         print(json.dumps(out), flush=True)
+
+
+DUMP_BYTES = 60_000_000   # all files of one --dump-outputs together
+
+
+def dump_outputs(args, comm, outputs) -> None:
+    """``--dump-outputs DIR``: rank 0 writes its local block of every array in ``outputs`` (what
+    the last timed step handed to its caller) as ``DIR/<name>.npy``. Floating-point arrays keep
+    float32 / become float64; integer arrays become float32 when every value is below 2^24 (exact),
+    else float64. The smallest arrays are written whole; one that does not fit into its share of
+    ``DUMP_BYTES`` is written as a 1-d sample at fixed, seeded flat indices (sorted, the same in every
+    run of the same arguments)."""
+    if not args.dump_outputs or comm.rank != 0:
+        return
+    import numpy as np
+
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    left = DUMP_BYTES
+    todo = sorted(outputs.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(todo):
+        t = t.detach()
+        if t.is_floating_point():
+            wide = t.dtype == torch.float64
+        else:
+            wide = bool(t.numel()) and int(t.abs().max()) >= 1 << 24
+        size = 8 if wide else 4
+        keep = left // (len(todo) - i) // size
+        if t.numel() > keep:
+            g = torch.Generator().manual_seed(20240229)
+            idx = torch.randint(t.numel(), (keep,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        arr = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+        left -= arr.nbytes
 
 
 def comm_ab_isolated(comm, sizes) -> dict:

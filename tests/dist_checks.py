@@ -700,7 +700,7 @@ def check_io_hdf5_netcdf():
             assert_array_equal(ht.load(os.path.join(d, "a.nc"), "var", split=rsplit), data)
     part = ht.load_hdf5(os.path.join(d, "a.h5"), "data", split=0, load_fraction=0.5)
     assert part.shape == (3, 5)
-    ref = "/root/reference/heat/datasets"
+    ref = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "datasets")
     if os.path.isdir(ref):
         iris_csv = ht.load_csv(os.path.join(ref, "iris.csv"), sep=";", split=0)
         assert ht.allclose(ht.load(os.path.join(ref, "iris.h5"), "data", split=0), iris_csv)

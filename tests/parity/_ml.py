@@ -7,7 +7,7 @@ import numpy as np
 
 import heat_amd as ht
 
-DS = "/root/reference/heat/datasets"
+DS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "golden", "datasets")
 
 
 def iris(split=None):

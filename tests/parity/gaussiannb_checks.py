@@ -11,7 +11,7 @@ import heat_amd as ht
 
 from ._util import close, raises, same
 
-DS = "/root/reference/heat/datasets"
+DS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "golden", "datasets")
 PRIOR = np.array([0.38666667, 0.26666667, 0.34666667])
 THETA = np.array([[4.97586207, 3.35862069, 1.44827586, 0.23448276], [5.935, 2.71, 4.185, 1.3],
                   [6.77692308, 3.09230769, 5.73461538, 2.10769231]])

@@ -12,7 +12,7 @@ import heat_amd as ht
 
 from ._util import close, raises, same, splits
 
-DS = "/root/reference/heat/datasets"
+DS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "golden", "datasets")
 CSV, H5, NC = os.path.join(DS, "iris.csv"), os.path.join(DS, "iris.h5"), os.path.join(DS, "iris.nc")
 
 

@@ -9,7 +9,7 @@ import heat_amd as ht
 
 from ._util import close, raises
 
-H5 = "/root/reference/heat/datasets/diabetes.h5"
+H5 = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "golden", "datasets", "diabetes.h5")
 
 
 def test_regressor():

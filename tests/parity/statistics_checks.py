@@ -11,7 +11,7 @@ import heat_amd as ht
 
 from ._util import close, raises, rng, same, splits
 
-IRIS = "/root/reference/heat/datasets/iris.csv"
+IRIS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "golden", "datasets", "iris.csv")
 
 
 def _iris(split):

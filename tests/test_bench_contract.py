@@ -29,7 +29,7 @@ def test_bench_multi_rank_one_json_line(ranks):
     env = dict(os.environ, HEAT_COMM_BACKEND="gloo", CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr",
            "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", str(ranks), "--steps", "2", "--warmup", "1",
-           "--n-per-gpu", "3000", "--exact-steps", "0"]
+           "--n-per-gpu", "3000", "--full", "--exact-steps", "0"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
@@ -61,7 +61,7 @@ def test_bench_secondary_workloads_validate(workload):
         workload, ["--rows", "6000", "--f", "8"])
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--workload", workload] + extra_args
+           "--full", "--workload", workload] + extra_args
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
@@ -91,7 +91,7 @@ def test_bench_self_launches_gpus_ranks():
     """``bench.py --gpus 4`` with no launcher starts 4 rank processes itself and relays ONE JSON
     line from rank 0 that saw a 4-rank device world."""
     cmd = [sys.executable, "bench.py", "--gpus", "4", "--steps", "2", "--warmup", "1", "--n-per-gpu", "3000",
-           "--exact-steps", "0"]
+           "--full", "--exact-steps", "0"]
     r = subprocess.run(cmd, cwd=ROOT, env=_clean_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
@@ -145,11 +145,70 @@ def test_check_labels_catches_a_wrong_assignment():
     assert abs(res["label_agreement"] - 0.99) < 1e-3
 
 
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run only times its ``--steps`` steps (none of the ``--full`` checks or side
+    measurements in ``extra``); ``--dump-outputs`` writes the last step's arrays as float32 /
+    float64 ``.npy`` files that a second run of the same arguments reproduces exactly."""
+    import numpy as np
+
+    runs = []
+    for name in ("a", "b"):
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--n-per-gpu", "3000",
+               "--k", "16", "--dump-outputs", str(tmp_path / name)]
+        r = subprocess.run(cmd, cwd=ROOT, env=_clean_env(), capture_output=True, text=True, timeout=240)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1, r.stdout
+        rec = lines[0]
+        assert KEYS <= set(rec) and rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert rec["metric"] == "kmeans_iter_gflops" and rec["dtype"] == "fp32" and rec["higher_is_better"] is True
+        moved = {"world_size_seen_by_rccl", "centroids_agree", "labels_ok", "allreduce_us", "exact_ms_per_step",
+                 "reference_impl_ms", "comm_ab"}
+        assert not moved & set(rec["extra"])
+        runs.append({f: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
+    a, b = runs
+    assert sorted(a) == ["centroid_shift.npy", "cluster_centers.npy", "labels.npy"]
+    assert a["cluster_centers.npy"].shape == (16, 64) and a["labels.npy"].shape[0] == 3000
+    assert sum(v.nbytes for v in a.values()) <= 64 * 1000 * 1000
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64)
+        np.testing.assert_array_equal(a[f], b[f])
+    lab = a["labels.npy"].reshape(-1)
+    assert lab.min() >= 0 and lab.max() < 16 and np.all(lab == np.round(lab))
+
+
+def test_dump_outputs_samples_what_exceeds_the_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs: small arrays whole, a too-large one as a fixed sample within the budget;
+    integers become float32 only while that is exact."""
+    import types
+
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from heat_amd.core.communication import MPI_WORLD
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4000)
+    big = torch.arange(5000, dtype=torch.float32).reshape(50, 100)
+    outs = {"big": big, "small": torch.tensor([[1, 2], [3, 4]], dtype=torch.int32),
+            "wide": torch.tensor([1 << 30, 5], dtype=torch.int64)}
+    for name in ("a", "b"):
+        bench.dump_outputs(types.SimpleNamespace(dump_outputs=str(tmp_path / name)), MPI_WORLD, outs)
+    got = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert got["small.npy"].dtype == np.float32 and got["small.npy"].tolist() == [[1, 2], [3, 4]]
+    assert got["wide.npy"].dtype == np.float64 and got["wide.npy"].tolist() == [float(1 << 30), 5.0]
+    s = got["big.npy"]
+    assert s.ndim == 1 and 0 < s.size < 5000 and sum(v.nbytes for v in got.values()) <= 4000
+    assert np.all(np.diff(s) >= 0) and set(s.tolist()) <= set(range(5000))
+    np.testing.assert_array_equal(s, np.load(tmp_path / "b" / "big.npy"))
+
+
 def test_bench_shared_gpu_rehearsal_records_itself():
     """HEAT_BENCH_SHARED_GPU=1: the N-rank job runs on a gloo world whatever the device count and
     the record says shared_gpu (never a scaling point)."""
     cmd = [sys.executable, "bench.py", "--gpus", "3", "--steps", "1", "--warmup", "1", "--n-per-gpu", "2000",
-           "--exact-steps", "0", "--comm-ab", "0"]
+           "--full", "--exact-steps", "0", "--comm-ab", "0"]
     r = subprocess.run(cmd, cwd=ROOT, env=_clean_env(HEAT_BENCH_SHARED_GPU="1"), capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]

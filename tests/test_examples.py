@@ -45,19 +45,14 @@ def test_datasets():
 
 
 def test_dataset_fixtures(monkeypatch):
-    """The reference fixtures (when a Heat checkout or $HEAT_DATASETS_DIR provides them) load through
-    every format with the same values, on every split axis; iris() / diabetes() return them."""
+    """The reference fixtures (the copies under tests/golden/datasets, found through
+    $HEAT_DATASETS_DIR) load through every format with the same values, on every split axis;
+    iris() / diabetes() return them."""
     import numpy as np
     import pytest
     import heat_amd as ht
 
-    import os
-
-    ref_dir = "/root/reference/heat/datasets"   # a Heat checkout, opted in through the env var
-    if not os.environ.get("HEAT_DATASETS_DIR") and os.path.isdir(ref_dir):
-        monkeypatch.setenv("HEAT_DATASETS_DIR", ref_dir)
-    if ht.datasets.fixture_path("iris.csv") is None:
-        pytest.skip("reference fixtures not available")
+    monkeypatch.setenv("HEAT_DATASETS_DIR", os.path.join(REPO, "tests", "golden", "datasets"))
     ref = np.loadtxt(ht.datasets.fixture_path("iris.csv"), delimiter=";", dtype=np.float32)
     assert ref.shape == (150, 4)
     for name in ("iris.csv", "iris.h5", "iris.nc"):
