@@ -128,6 +128,16 @@ def _native_fp32(a: torch.Tensor, b: torch.Tensor) -> bool:
     return ops.use_native(a)
 
 
+def _native_fp64(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """Device float64 operands on the hand-written fp64 MFMA kernel (``ops.gemm_f64``) unless
+    ``HEAT_GEMM_BACKEND=blas``."""
+    if _GEMM_BACKEND != "native" or not (a.is_cuda and a.dtype == torch.float64 and b.dtype == torch.float64):
+        return False
+    from ... import ops
+
+    return ops.use_native(a)
+
+
 _GEMM_PLAN = os.environ.get("HEAT_GEMM_PLAN", "1") != "0"   # 0: the library for the small products
 
 
@@ -197,15 +207,87 @@ def _library_better(M: int, N: int, K: int, exact: bool) -> bool:
     return tiles < (4 * ncu if exact else ncu)
 
 
+@functools.lru_cache(maxsize=1024)
+def _library_better_f64(M: int, N: int, K: int, gram: bool) -> bool:
+    """The fp64 products that go to the library DGEMM: those whose 128 x 128 output tiles fill the
+    2 x CUs workgroup slots of ``ops.gemm_f64`` poorly and have no deep K to split. An f64 MFMA takes
+    64 cycles, so a tile costs K / 8 x 2048 cycles per wave however few tiles there are.
+    Measured, ops.gemm_f64 vs torch.matmul alternating in one process, ms native / library
+    (``tools/microbench/gemm_f64.py``: profiles/gemm_f64_r07.jsonl, and its ``--shapes`` / ``--gram``
+    rows in gemm_f64_r07_shapes.jsonl / gemm_f64_r07_gram.jsonl).
+
+    Fewer tiles than CUs -> library unless K >= max(4096, 8 max(M, N)):
+    library side - 64^2 x 900 0.120 / 0.018, 10^2 x 1000 0.126 / 0.019, 128^2 x 2000 0.090 / 0.065,
+    256^2 x 2048 0.071 / 0.043, 300^2 x 3000 0.088 / 0.062, 700 x 520 x 300 0.048 / 0.013, 512^3 0.068 /
+    0.012, 512^2 x 2048 0.073 / 0.043, 600^2 x 3000 0.093 / 0.063, 1024^2 x 256 0.039 / 0.012, 1024^3
+    0.080 / 0.040, x 2048 0.089 / 0.076, x 4096 0.160 / 0.138, x 6144 0.214 / 0.194, 1536^3 0.158 / 0.134,
+    2048 x 1024^2 0.092 / 0.075, 6000 x 600^2 0.097 / 0.081;
+    native side (split-K) - 64^2 x 4096 0.076 / 0.069, 256^2 x 4096 0.072 / 0.082, 512^2 x 4096 0.075 /
+    0.127, 600^2 x 6000 0.146 / 0.184, 1024^2 x 8192 0.29 / 0.89, 128^2 x 16384 0.079 / 1.77, 256^2 x
+    65536 0.20 / 7.0, 32^2 x 1e5 0.12 / 10.7, 512^2 x 1e6 8.7 / 107, 16^2 x 1e6 0.60 / 107.
+
+    From one tile per CU on, the last wave decides (the cost model of :func:`_native_plan`): w =
+    tiles / slots waves of work take floor(w) + 1 waves, or + 0.575 when the last wave has at most
+    one workgroup per CU (alone on its CU it runs 1.74x faster); efficiency below 0.8 -> library:
+    library side - 2304^3 (324 tiles, 0.63) 0.553 / 0.406, 2560^3 (400, 0.78) 0.614 / 0.525, 2560^2 x
+    8192 1.95 / 1.79, 3072^3 (576, 0.71) 1.106 / 0.850, 3072^2 x 512 0.193 / 0.153, 20000 x 512^2 (628,
+    0.78) 0.197 / 0.188, 3584^3 (784, 0.77) 1.715 / 1.589 - the last two within 10 % either way;
+    native side - 2048^3 (256, 0.87; two K slices) 0.277 / 0.254, 2048^2 x 512 0.076 / 0.073, 2816^3 (484,
+    0.95) 0.677 / 0.669, 3328^3 (676, 0.84) 1.197 / 1.102, 3840^3 (900, 0.88) 1.825 / 1.693, 4096^3 1.94 /
+    1.94, 4608^3 (1296, 0.84) 3.32 / 3.08, 5120^3 (1600, 0.87) 4.31 / 4.46, 5632^3 5.39 / 5.08, 6144^3
+    6.59 / 6.81, 8192^3 15.5 / 15.2, 40000 x 2048 x 256 0.664 / 0.633, 1.25e5 x 4096^2 59.7 / 57.8.
+
+    Gram products (upper tiles + mirror; the library runs the transposed view slower) with fewer
+    tiles than CUs: native from K >= max(2048, 4 n) when there are at most CUs / 8 tiles - 512^2 x
+    2048 0.092 / 0.115, x 4096 0.094 / 0.128, 600^2 x 3000 0.103 / 0.168, x 6000 0.152 / 0.167, x 20000
+    0.26 / 1.08 - and otherwise as a plain product: 1024^2 x 3000 0.183 / 0.109 and x 4096 0.169 /
+    0.133 library, x 8192 0.296 / 0.890 native (2048^2 x 1e5, 256 tiles: 11.75 / 11.91).
+
+    Between the measured rows the rule extrapolates: M, N < 256 with 4096 <= K, tile counts
+    between those listed, and Gram products from one tile per CU on are not measured further."""
+    from ... import ops
+
+    ncu = ops.num_cus(torch.device("cuda", torch.cuda.current_device())) if torch.cuda.is_available() else 256
+    tiles = -(-M // 128) * -(-N // 128)
+    if tiles < ncu:
+        if gram and 8 * tiles <= ncu:
+            return K < max(2048, 4 * max(M, N))
+        return K < max(4096, 8 * max(M, N))
+    w = tiles / (2.0 * ncu)
+    full, frac = int(w), w - int(w)
+    waves = full + (0.575 if 0 < frac <= 0.5 else (1 if frac > 0 else 0))
+    return w / waves < 0.8
+
+
 def fgemm(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, alpha: float = 1.0,
           accumulate: bool = False, b_upper: bool = False) -> torch.Tensor:
     """``alpha * a @ b`` (``+ out`` when ``accumulate``) for 2-D operands: device fp32 on the
     hand-written MFMA kernels - the fused fp16x3 kernel when the float32 matmul precision allows it,
     else the exact f32-MFMA kernel (both 256 x 256 tiles, any operand layout, 64-bit offsets, so no
     blocking) - except products with too few output tiles to fill the GPU, which run on the library
-    with exact fp32 products (:func:`_library_better`); other dtypes / host tensors on torch
-    (blocked below the library's operand limit). ``b_upper``: b is square upper triangular (the
-    caller's guarantee, e.g. CholeskyQR's R^-1): the 256-tile kernels skip its zero half of K."""
+    with exact fp32 products (:func:`_library_better`); device fp64 on the fp64-MFMA kernel
+    (``ops.gemm_f64``: 128 x 128 tiles, any operand layout, 64-bit offsets, split-K for few output
+    tiles, Gram products on the upper tiles + a mirror; no blocking) except few-tile short-K
+    products, which the library runs faster (:func:`_library_better_f64`); other dtypes / host tensors
+    on torch (blocked below the library's operand limit). ``b_upper``: b is square upper
+    triangular (the caller's guarantee, e.g. CholeskyQR's R^-1): the 256-tile kernels skip its
+    zero half of K."""
+    if _native_fp64(a, b):
+        from ... import ops
+        from ...ops import kernels as _kern
+
+        gram = a.shape[0] == b.shape[1] >= _GRAM_MIN_N and a.shape[1] >= a.shape[0] and \
+            (_kern._is_gram(a, b) or _kern._is_gram(b, a))
+        if _library_better_f64(a.shape[0], b.shape[1], a.shape[1], gram):
+            pass                     # few output tiles, short K: the library (generic path below)
+        elif gram:
+            u = ops.gemm_f64(a, b, alpha=alpha, upper=True)   # X^T X / X X^T: upper tiles once + mirror
+            g = u + torch.triu(u, 1).t()
+            if out is None:
+                return g
+            return out.add_(g) if accumulate else out.copy_(g)
+        else:
+            return ops.gemm_f64(a, b, out=out, alpha=alpha, accumulate=accumulate)
     if _native_fp32(a, b) and a.shape[0] == b.shape[1] >= _GRAM_MIN_N and a.shape[1] >= a.shape[0]:
         from ... import ops
 
@@ -262,9 +344,9 @@ def _leaf_mm(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 
 def _mm(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """``a @ b``: device fp32 matrices on the hand-written kernels (:func:`fgemm`), everything else
-    through :func:`_mm_blocked`."""
-    if a.dim() == 2 and b.dim() == 2 and _native_fp32(a, b):
+    """``a @ b``: device fp32 and fp64 matrices on the hand-written kernels (:func:`fgemm`),
+    everything else through :func:`_mm_blocked`."""
+    if a.dim() == 2 and b.dim() == 2 and (_native_fp32(a, b) or _native_fp64(a, b)):
         return fgemm(a, b)
     return _mm_blocked(a, b)
 

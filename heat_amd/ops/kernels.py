@@ -20,7 +20,7 @@ from . import check, lib, stream_ptr, use_native
 __all__ = ["kmeans_finalize", "pack_blocks", "unpack_blocks", "pack_supported", "kmeans_assign", "kmeans_pack_points", "PackedPoints", "cdist_pack", "PackedRows", "kmeans_update", "moments", "merge_moments", "num_cus", "cdist", "lasso_epoch", "lasso_prepare", "LassoSweep", "gemm_f16x3",
            "split_planes", "gram_product", "gemm_f32_small", "knn_topk", "kmeans_step_small", "kmeans_lloyd_small", "lasso_gram", "lasso_cd", "argreduce_keys",
            "argreduce_decode", "argreduce_supported", "topk_rows", "gemm_f32", "gemm_h3", "h3_planes", "H3Planes",
-           "gemm_h3_planes", "gemm64", "cholesky_upper", "tri_inv_upper", "householder_qr",
+           "gemm_h3_planes", "gemm64", "gemm_f64", "cholesky_upper", "tri_inv_upper", "householder_qr",
            "householder_factor", "householder_apply", "householder_block", "vtc64", "gram64",
            "radix_sort_supported", "sort_rows"]
 
@@ -1540,6 +1540,51 @@ def gemm64(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None,
     check(lib().ha_gemm64(_ptr(A), _ptr(B), _ptr(out), M, N, K, lda, ldb, out.stride(0) if M > 1 else N, int(a_km),
                           int(not b_nm), int(upper), 1, 0, 0, 0, float(alpha), float(beta),
                           ctypes.c_void_p(stream_ptr(a.device))), "ha_gemm64")
+    return out
+
+
+def gemm_f64(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None, alpha: float = 1.0,
+             accumulate: bool = False, upper: bool = False, slices: Optional[int] = None) -> torch.Tensor:
+    """fp64 ``alpha * a @ b`` (``+ out`` when ``accumulate``) on the fp64 matrix cores: the
+    128 x 128-tile LDS-DMA pipelined kernel of ``csrc/gemm_f64.hip`` (v_mfma_f64_16x16x4_f64),
+    every operand layout (row-/column-major views such as ``x.T @ x``) without a copy, 64-bit
+    offsets. 16-byte aligned operands with even leading dimensions run on it; others on ``gemm64``
+    inside the same native call. ``out``: a row-major fp64 [M, N] view (e.g. a row block of a
+    larger result). ``upper``: only the entries with ``j >= i`` are computed and written (a new
+    ``out`` is zero elsewhere). ``slices``: K slices of the split-K form (fp64 partials summed in
+    slice order, bit-identical run to run); None picks ``ha_gemm_f64_slices``. Host tensors, other
+    dtypes and ``use_native`` false: torch."""
+    M, K = a.shape
+    N = b.shape[1]
+    if b.shape[0] != K:
+        raise ValueError("gemm_f64: inner dimensions differ: {} vs {}".format(K, b.shape[0]))
+    if not (_native64(a) and _native64(b)):
+        res = alpha * (a @ b) if alpha != 1.0 else a @ b
+        if upper:
+            res = torch.triu(res)
+        if out is None:
+            return res
+        if accumulate:
+            return out.add_(res)
+        return out.copy_(torch.where(torch.ones_like(res, dtype=torch.bool).triu(), res, out) if upper else res)
+    if out is None:
+        out = torch.zeros((M, N), dtype=torch.float64, device=a.device) if (accumulate or upper) else \
+            torch.empty((M, N), dtype=torch.float64, device=a.device)
+    elif out.shape != (M, N) or out.dtype != torch.float64 or (N > 1 and out.stride(1) != 1):
+        raise ValueError("gemm_f64: out must be a row-major float64 [M, N] tensor")
+    if M == 0 or N == 0:
+        return out
+    if K == 0:
+        return out if accumulate else (out.tril_(-1) if upper else out.zero_())
+    A, lda, a_km = _gemm_operand(a, 1)      # row-major: k contiguous; k-major: m contiguous
+    B, ldb, b_nm = _gemm_operand(b, 1)      # k-major: n contiguous; n-major: k contiguous
+    L = lib()
+    if slices is None:
+        slices = L.ha_gemm_f64_slices(M, N, K, num_cus(a.device))
+    P = torch.empty(slices * M * N, dtype=torch.float64, device=a.device) if slices > 1 else None
+    check(L.ha_gemm_f64(_ptr(A), _ptr(B), _ptr(out), M, N, K, lda, ldb, out.stride(0) if M > 1 else N, int(a_km),
+                        int(not b_nm), float(alpha), int(accumulate), int(upper), int(slices), _ptr(P),
+                        ctypes.c_void_p(stream_ptr(a.device))), "ha_gemm_f64")
     return out
 
 
