@@ -17,7 +17,7 @@ import torch.nn.functional as F
 
 from . import check, lib, stream_ptr, use_native
 
-__all__ = ["kmeans_finalize", "pack_blocks", "unpack_blocks", "pack_supported", "kmeans_assign", "kmeans_pack_points", "PackedPoints", "cdist_pack", "PackedRows", "kmeans_update", "moments", "merge_moments", "num_cus", "cdist", "lasso_epoch", "lasso_prepare", "LassoSweep", "gemm_f16x3",
+__all__ = ["kmeans_finalize", "pack_blocks", "unpack_blocks", "pack_supported", "kmeans_assign", "kmeans_pack_points", "PackedPoints", "cdist_pack", "PackedRows", "kmeans_update", "moments", "merge_moments", "num_cus", "cdist", "cdist_f64", "lasso_epoch", "lasso_prepare", "LassoSweep", "gemm_f16x3",
            "split_planes", "gram_product", "gemm_f32_small", "knn_topk", "kmeans_step_small", "kmeans_lloyd_small", "lasso_gram", "lasso_cd", "argreduce_keys",
            "argreduce_decode", "argreduce_supported", "topk_rows", "gemm_f32", "gemm_h3", "h3_planes", "H3Planes",
            "gemm_h3_planes", "gemm64", "gemm_f64", "cholesky_upper", "tri_inv_upper", "householder_qr",
@@ -644,7 +644,9 @@ def cdist(X: torch.Tensor, Y: torch.Tensor, metric: str = "euclidean", sigma: fl
           out: Optional[torch.Tensor] = None, exact: bool = False, precision: str = "f16x3",
           packed_x: Optional[PackedRows] = None, packed_y: Optional[PackedRows] = None,
           symmetric: bool = False) -> torch.Tensor:
-    """Pairwise distances between the rows of X [m, f] and Y [n, f] as an [m, n] float32 matrix.
+    """Pairwise distances between the rows of X [m, f] and Y [n, f] as an [m, n] matrix: float32,
+    or float64 when both operands are device float64 tensors (:func:`cdist_f64`; ``precision`` and
+    the packed operands are ignored there).
 
     Device tensors, L2 family with ``exact=False`` (quadratic expansion, fused norm/clamp/
     sqrt|exp epilogue): ``precision="f16x3"`` -> 3-term fp16 split on the FP16 matrix cores
@@ -688,6 +690,8 @@ def cdist(X: torch.Tensor, Y: torch.Tensor, metric: str = "euclidean", sigma: fl
                                 ctypes.c_void_p(stream_ptr(X.device)))
             check(rc, "ha_cdist")
         return C
+    if use_native(X) and Y.is_cuda and X.dtype == torch.float64 and Y.dtype == torch.float64:
+        return cdist_f64(X, Y, metric, sigma, out, exact, symmetric)
     Xf = X if X.is_floating_point() else X.float()
     Yf = Y.to(Xf.dtype)
     if metric == "manhattan":
@@ -710,6 +714,78 @@ def cdist(X: torch.Tensor, Y: torch.Tensor, metric: str = "euclidean", sigma: fl
         out.copy_(res)
         return out
     return res
+
+
+def _rows_f64_aligned(X: torch.Tensor) -> torch.Tensor:
+    """The rows of a device fp64 matrix as the expansion kernel of ``csrc/cdist_f64.hip`` reads them:
+    unit feature stride, even row stride, 16-byte aligned base and, for an odd feature count, a
+    readable element behind the last row. ``X`` itself when it already is all that, else a copy
+    with the rows zero-padded to an even length."""
+    m, f = X.shape
+    ok = X.stride(1) == 1 and X.data_ptr() % 16 == 0 and (m == 1 or (X.stride(0) % 2 == 0 and X.stride(0) >= f))
+    if ok and f % 2:
+        ok = X.storage_offset() + (m - 1) * X.stride(0) + f < X.untyped_storage().nbytes() // 8
+    if ok:
+        return X
+    P = torch.empty((m, f + f % 2), dtype=torch.float64, device=X.device)
+    P[:, :f] = X
+    P[:, f:] = 0
+    return P[:, :f]
+
+
+def cdist_f64(X: torch.Tensor, Y: torch.Tensor, metric: str = "euclidean", sigma: float = 1.0,
+              out: Optional[torch.Tensor] = None, exact: bool = False, symmetric: bool = False) -> torch.Tensor:
+    """float64 pairwise distances between the rows of the device float64 matrices X [m, f] and
+    Y [n, f] (``csrc/cdist_f64.hip``), written once by the tile kernel's own epilogue.
+
+    L2 family with ``exact=False``: |x|^2 + |y|^2 - 2 x.y on the fp64 matrix cores (an operand is
+    copied only if it is not 16-byte aligned with an even row stride; ``Y is X`` once).
+    ``exact=True`` and manhattan: the difference kernel on the fp64 VALU, any row-strided views
+    without a copy; every pair is summed over the features in index order, so an entry does not
+    depend on the shapes or the tile it falls in. ``symmetric`` (``Y is X``, difference kernel):
+    tiles on or above the diagonal computed once and mirrored. ``out``: a float64 row-contiguous
+    matrix of at least m x n whose first m x n entries are written; it is returned as given."""
+    if X.ndim != 2 or Y.ndim != 2 or X.shape[1] != Y.shape[1]:
+        raise ValueError("cdist_f64: X [m, f] and Y [n, f] must be matrices with the same feature count")
+    if metric not in _CDIST_MODES:
+        raise ValueError("unknown metric {}".format(metric))
+    if not (_native64(X) and _native64(Y)) or X.device != Y.device:
+        raise TypeError("cdist_f64 needs float64 tensors on one device")
+    (m, f), n = X.shape, Y.shape[0]
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float64, device=X.device)
+    elif (out.dtype != torch.float64 or out.ndim != 2 or out.device != X.device or out.shape[0] < m
+          or out.shape[1] < n or (out.shape[1] > 1 and out.stride(1) != 1)
+          or (out.shape[0] > 1 and out.stride(0) < out.shape[1])):
+        raise ValueError("cdist_f64: out must be a row-contiguous float64 matrix of at least {} x {}".format(m, n))
+    if m == 0 or n == 0:
+        return out
+    if f == 0:
+        out[:m, :n] = 1.0 if metric == "gaussian" else 0.0
+        return out
+    mode = (_CDIST_EXACT if exact else _CDIST_MODES)[metric]
+    ws = None
+    if mode < 3:
+        Xa = _rows_f64_aligned(X)
+        Ya = Xa if Y is X else _rows_f64_aligned(Y)
+        ws = torch.empty(m + n, dtype=torch.float64, device=X.device)
+    else:
+        Xa = X if X.stride(1) == 1 and (m == 1 or X.stride(0) >= f) else X.contiguous()
+        Ya = Xa if Y is X else (Y if Y.stride(1) == 1 and (n == 1 or Y.stride(0) >= f) else Y.contiguous())
+
+    def ld(t):   # a single row has no stride
+        return t.stride(0) if t.shape[0] > 1 else f + f % 2
+
+    sym = symmetric and mode >= 3 and Y is X
+    L, st = lib(), ctypes.c_void_p(stream_ptr(X.device))
+    ldc = out.stride(0) if out.shape[0] > 1 else max(out.shape[1], n)
+    scale = 1.0 / (2.0 * sigma * sigma)
+    rc = L.ha_cdist_f64(_ptr(Xa), m, _ptr(Ya), n, f, ld(Xa), ld(Ya), _ptr(out), ldc, mode | (256 if sym else 0),
+                        scale, _ptr(ws), st)
+    if sym and rc == _HA_UNSUPPORTED:
+        rc = L.ha_cdist_f64(_ptr(Xa), m, _ptr(Ya), n, f, ld(Xa), ld(Ya), _ptr(out), ldc, mode, scale, _ptr(ws), st)
+    check(rc, "ha_cdist_f64")
+    return out
 
 
 # --------------------------------------------------------------------------------------------- lasso

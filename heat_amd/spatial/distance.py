@@ -142,7 +142,7 @@ def _dist(X: DNDarray, Y: Optional[DNDarray] = None, metric="euclidean", sigma: 
     def tile(block: torch.Tensor, src: int):
         c0, cn = displs[src], counts[src]
         if cn and x.shape[0]:
-            if tt == torch.float32 and out.is_cuda:
+            if out.is_cuda:   # float32 and float64 tiles are written in place by the native kernels
                 _local(metric, x, block, sigma, out=out[:, c0: c0 + cn])
             else:
                 out[:, c0: c0 + cn] = _local(metric, x, block, sigma)
