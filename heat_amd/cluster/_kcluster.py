@@ -151,7 +151,14 @@ class _KCluster(ClusteringMixin, BaseEstimator):
         X = x.larray
         first = int(ht.random.randint(0, n, size=(1,), device="cpu").larray.item())
         cents = [self._rows(x, torch.tensor([first]))[0]]
-        d2 = ((X - cents[0]) ** 2).sum(1)
+
+        def to_row(row):
+            # device float64: the fused fp64 kernel against the one new centroid (no n x f temporary)
+            if X.dtype == torch.float64 and X.shape[0] > 0 and ops.use_native(X):
+                return ops.kmeans_assign_f64(X, row.reshape(1, -1))[1]
+            return ((X - row) ** 2).sum(1)
+
+        d2 = to_row(cents[0])
         counts, displs = (x.counts_displs() if x.is_distributed() else ((n,), (0,)))
         me = x.comm.rank if x.is_distributed() else 0
         for _ in range(1, k):
@@ -173,7 +180,7 @@ class _KCluster(ClusteringMixin, BaseEstimator):
             if x.is_distributed():
                 x.comm.Bcast(row, root=owner)
             cents.append(row)
-            d2 = torch.minimum(d2, ((X - row) ** 2).sum(1))
+            d2 = torch.minimum(d2, to_row(row))
         return torch.stack(cents)
 
     def _assign_to_cluster(self, x: DNDarray) -> DNDarray:

@@ -6,7 +6,8 @@ Per iteration and rank: ONE fused assign kernel (distances as a 3-term fp16 spli
 matrix cores, ~fp32-GEMM accuracy, plus a running argmax of the score; the points' fp16 planes are
 packed once per fit - ``ops/csrc/kmeans_f16x3.hip``; a certified one-term filter with a 3-term
 re-check where it pays; k <= 16 a single fused VALU/MFMA pass, ``kmeans_smallk.hip``; the exact
-f32-MFMA kernel under ``precision="exact"``), ONE deterministic update (counting sort of the
+f32-MFMA kernel under ``precision="exact"``; float64 points: the fp64-MFMA kernel of
+``kmeans_f64.hip``, float64 sums, counts and centroids end to end), ONE deterministic update (counting sort of the
 labels, fixed-order per-cluster sums and counts - ``kmeans.hip``: no float atomics, bit-reproducible
 runs) and ONE all-reduce of the packed (k*f sums + k counts) over RCCL - instead of the reference's
 k full passes over the data and 2k all-reduces + k broadcasts.
@@ -73,7 +74,7 @@ class KMeans(_KCluster):
         k = self.n_clusters
         labels = matching_centroids.larray.reshape(-1).to(torch.int32)
         X = x.larray
-        sums, counts = ops.kmeans_update(X if X.dtype == torch.float32 else X.float(), labels, k)
+        sums, counts = ops.kmeans_update(X if X.dtype in (torch.float32, torch.float64) else X.float(), labels, k)
         packed = torch.cat([sums.reshape(-1).double(), counts.double()])
         if x.is_distributed():
             x.comm.Allreduce(MPI.IN_PLACE, packed, MPI.SUM)
@@ -91,6 +92,8 @@ class KMeans(_KCluster):
 
         if os.environ.get("HEAT_KMEANS_GRAPH", "0") != "1" or not X.is_cuda:
             return False
+        if X.dtype == torch.float64:
+            return False  # the float64 step (ops/csrc/kmeans_f64.hip) has not been replayed from a graph
         # Measured on MI355X / ROCm 7 (tools/microbench/graph_debug2.py): with the runtime's graph
         # packet capture (the default), replays of a step containing a 256 KB memset node went wrong
         # from the second replay (centroids diverged to 1e27); with

@@ -456,6 +456,106 @@ __global__ __launch_bounds__(256) void ku_reduce_det(const float* __restrict__ P
   sums[e] = (float)s;
 }
 
+// -------------------------------------------------------------- deterministic update, fp64 points
+// The label ordering above (ku_hist, ku_scan_*, ku_scatter_det) does not depend on the data type;
+// these are the fp64 forms of the gather and the reduction. A lane loads two doubles of a row (16
+// bytes), 16 lanes cover 32 columns per pass; a (range, column-pair) thread sums its 256 sorted
+// positions sequentially into its own (cluster + range) slot, and the range partials of a cluster
+// are added in range order: no atomics, the same bits on every run.
+typedef double ku_doublex2 __attribute__((ext_vector_type(2)));
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void ku_gather_det_f64(const double* __restrict__ X, int f, int64_t ldx,
+                                                         const int* __restrict__ order,
+                                                         const int* __restrict__ cstart, int k,
+                                                         double* __restrict__ P) {
+  const int cg = threadIdx.x & 15, rl = threadIdx.x >> 4;
+  const int64_t nvalid = cstart[k];
+  const int64_t rg = (int64_t)blockIdx.x * 16 + rl;
+  const int64_t p0 = rg * KU_RANGE;
+  if (p0 >= nvalid) return;
+  const int64_t p1 = p0 + KU_RANGE < nvalid ? p0 + KU_RANGE : nvalid;
+  const int c0 = ku_cluster_of(cstart, k, p0);
+  for (int cb = 0; cb < f; cb += 32) {
+    const int col = cb + 2 * cg;
+    if (col >= f) break;
+    int cur = c0;
+    int64_t nb = cstart[cur + 1];
+    ku_doublex2 acc = (ku_doublex2)(0.0);
+    auto flush = [&]() {
+      double* d = P + ((int64_t)cur + rg) * f + col;
+      if (VEC) {
+        *reinterpret_cast<ku_doublex2*>(d) = acc;
+      } else {
+        d[0] = acc[0];
+        if (col + 1 < f) d[1] = acc[1];
+      }
+      acc = (ku_doublex2)(0.0);
+    };
+    auto row = [&](int idx) {
+      const double* src = X + (int64_t)idx * ldx + col;
+      if (VEC) return __builtin_nontemporal_load(reinterpret_cast<const ku_doublex2*>(src));  // streamed once
+      ku_doublex2 v;
+      v[0] = src[0];
+      v[1] = col + 1 < f ? src[1] : 0.0;
+      return v;
+    };
+    int64_t q = p0;
+    for (; q + KU_RD <= p1; q += KU_RD) {
+      int idx[KU_RD];
+      ku_doublex2 v[KU_RD];
+#pragma unroll
+      for (int u = 0; u < KU_RD; ++u) idx[u] = order[q + u];
+#pragma unroll
+      for (int u = 0; u < KU_RD; ++u) v[u] = row(idx[u]);
+#pragma unroll
+      for (int u = 0; u < KU_RD; ++u) {
+        while (q + u >= nb) {
+          flush();
+          ++cur;
+          nb = cstart[cur + 1];
+        }
+        acc += v[u];
+      }
+    }
+    for (; q < p1; ++q) {
+      const ku_doublex2 v = row(order[q]);
+      while (q >= nb) {
+        flush();
+        ++cur;
+        nb = cstart[cur + 1];
+      }
+      acc += v;
+    }
+    flush();
+  }
+}
+
+// sums[c] = the cluster's range partials in range order; element e < k also writes counts[e]
+__global__ __launch_bounds__(256) void ku_reduce_det_f64(const double* __restrict__ P, const int* __restrict__ cstart,
+                                                         int k, int f, double* __restrict__ sums,
+                                                         double* __restrict__ counts) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e < k) counts[e] = (double)(cstart[e + 1] - cstart[e]);
+  if (e >= (int64_t)k * f) return;
+  const int c = (int)(e / f), j = (int)(e % f);
+  const int64_t a = cstart[c], b = cstart[c + 1];
+  double s = 0.0;
+  if (b > a) {
+    const int64_t rlo = a / KU_RANGE, rhi = (b - 1) / KU_RANGE;
+    int64_t r = rlo;
+    for (; r + 8 <= rhi + 1; r += 8) {  // 8 loads in flight, added in range order
+      double v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = P[((int64_t)c + r + u) * f + j];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += v[u];
+    }
+    for (; r <= rhi; ++r) s += P[((int64_t)c + r) * f + j];
+  }
+  sums[e] = s;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ C ABI
@@ -545,5 +645,63 @@ HA_EXPORT int ha_km_update(const float* X, int64_t n, int f, int64_t ldx, const 
   else
     hipLaunchKernelGGL(ku_gather, dim3((unsigned)((n + KU_CHUNK - 1) / KU_CHUNK)), dim3(256), 0, s, X, f, ldx,
                        order, cstart, k, sums);
+  return ha_launch_status();
+}
+
+// int32 scratch ha_km_update_f64 needs (-1: unsupported k or n): the order array, histograms,
+// totals, segment starts and the scan's fp32 counts, plus the gather's (k + ranges) x f fp64
+// partials behind a 16-byte boundary.
+HA_EXPORT int64_t ha_km_update_f64_workspace(int64_t n, int k, int f) {
+  if (k <= 0 || f <= 0 || n < 0 || (int64_t)k * 4 > 150 * 1024 || n >= (int64_t)1 << 31) return -1;
+  int64_t nblk, rows;
+  ku_grid(n, &nblk, &rows);
+  const int64_t nranges = (n + KU_RANGE - 1) / KU_RANGE;
+  return n + nblk * k + k + (k + 1) + k + 4 + 2 * (k + nranges) * (int64_t)f;
+}
+
+// fp64 points: sums [k][f] and counts [k] (fp64) are written completely, by the deterministic
+// pipeline only; labels outside [0, k) are ignored. X needs 8-byte alignment and feature stride 1;
+// rows are read 16 bytes per lane where X is 16-byte aligned and f, ldx are even. workspace must be
+// 16-byte aligned.
+HA_EXPORT int ha_km_update_f64(const double* X, int64_t n, int f, int64_t ldx, const int* labels, int k, double* sums,
+                               double* counts, int* workspace, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n <= 0 || !X || !labels || !sums || !counts || !workspace || (n > 1 && ldx < f) ||
+      (reinterpret_cast<uintptr_t>(workspace) & 15))
+    return HA_BAD_ARG;
+  if (ha_km_update_f64_workspace(n, k, f) < 0) return HA_UNSUPPORTED;
+  int64_t nblk, rows;
+  ku_grid(n, &nblk, &rows);
+  int* order = workspace;
+  int* hist = order + n;
+  int* total = hist + nblk * k;
+  int* cstart = total + k;
+  float* fcounts = reinterpret_cast<float*>(cstart + k + 1);
+  const size_t lds = (size_t)k * sizeof(int);
+  if (lds > 64 * 1024) hipFuncSetAttribute((const void*)ku_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(ku_hist, dim3((unsigned)nblk), dim3(KU_BLOCK), lds, s, labels, n, k, rows, hist,
+                     (float*)nullptr, (int64_t)0);
+  hipLaunchKernelGGL(ku_scan_blk, dim3((k + 255) / 256), dim3(256), 0, s, hist, (int)nblk, k, total);
+  hipLaunchKernelGGL(ku_scan_tot, dim3(1), dim3(1024), 0, s, total, k, cstart, fcounts);
+  // waves per scatter block: their per-wave counts ([W][k] ints) must fit in LDS
+  int W = 16;
+  while (W > 1 && (size_t)W * k * sizeof(int) > 128 * 1024) W >>= 1;
+  const size_t lds_det = (size_t)W * k * sizeof(int);
+  if (lds_det > 64 * 1024)
+    hipFuncSetAttribute((const void*)ku_scatter_det, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_det);
+  hipLaunchKernelGGL(ku_scatter_det, dim3((unsigned)nblk), dim3(64 * W), lds_det, s, labels, n, k, rows, W, hist,
+                     cstart, order);
+  int64_t off = (int64_t)((fcounts + k) - reinterpret_cast<float*>(workspace));
+  off = (off + 3) & ~(int64_t)3;
+  double* P = reinterpret_cast<double*>(workspace + off);
+  const int64_t nranges = (n + KU_RANGE - 1) / KU_RANGE;
+  const unsigned gblk = (unsigned)((nranges + 15) / 16);
+  if (f % 2 == 0 && ldx % 2 == 0 && ((uintptr_t)X & 15) == 0)
+    hipLaunchKernelGGL(ku_gather_det_f64<true>, dim3(gblk), dim3(256), 0, s, X, f, ldx, order, cstart, k, P);
+  else
+    hipLaunchKernelGGL(ku_gather_det_f64<false>, dim3(gblk), dim3(256), 0, s, X, f, ldx, order, cstart, k, P);
+  const int64_t relems = (int64_t)k * f > k ? (int64_t)k * f : k;
+  hipLaunchKernelGGL(ku_reduce_det_f64, dim3((unsigned)((relems + 255) / 256)), dim3(256), 0, s, P, cstart, k, f,
+                     sums, counts);
   return ha_launch_status();
 }

@@ -6,6 +6,7 @@
 //   shift      = sum (C[c, j] - newC[c, j])^2      (fp64)
 // Sums and counts are fp64 (the packed all-reduce buffer [sums | counts] of a distributed step) or
 // fp32 (the update kernel's own output on a world of one: no cast/pack kernels in between).
+// The centroids are fp32, or fp64 with fp64 sums (ha_km_finalize_f64: device float64 k-means).
 // The shift is reduced without atomics on one address and without a memset launch: every block
 // writes its partial, and the last block to finish (a self-resetting arrival counter in `ws`)
 // adds them in a fixed order, so the result is also deterministic.
@@ -15,18 +16,18 @@ namespace {
 
 constexpr int FIN_MAX_BLOCKS = 256;
 
-template <typename T>
+template <typename T, typename TC>
 __global__ __launch_bounds__(256) void km_finalize(const T* __restrict__ sums, const T* __restrict__ counts, int k,
-                                                   int f, const float* __restrict__ C, int64_t ldc,
-                                                   float* __restrict__ newC, double* __restrict__ shift,
+                                                   int f, const TC* __restrict__ C, int64_t ldc,
+                                                   TC* __restrict__ newC, double* __restrict__ shift,
                                                    double* __restrict__ part, unsigned* __restrict__ arrived) {
   const int kf = k * f;
   double acc = 0.0;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < kf; i += gridDim.x * 256) {
     const int c = i / f, j = i - c * f;
     const double cnt = (double)counts[c];
-    const float old = C[(int64_t)c * ldc + j];
-    const float nv = cnt > 0.0 ? (float)((double)sums[i] / cnt) : old;
+    const TC old = C[(int64_t)c * ldc + j];
+    const TC nv = cnt > 0.0 ? (TC)((double)sums[i] / cnt) : old;
     newC[i] = nv;
     const double d = (double)old - (double)nv;
     acc = fma(d, d, acc);
@@ -55,8 +56,8 @@ __global__ __launch_bounds__(256) void km_finalize(const T* __restrict__ sums, c
   }
 }
 
-template <typename T>
-int launch(const T* sums, const T* counts, int k, int f, const float* C, int64_t ldc, float* newC, double* shift,
+template <typename T, typename TC>
+int launch(const T* sums, const T* counts, int k, int f, const TC* C, int64_t ldc, TC* newC, double* shift,
            void* ws, hipStream_t s) {
   const int64_t kf = (int64_t)k * f;
   int64_t blocks = (kf + 256 * 4 - 1) / (256 * 4);
@@ -64,7 +65,7 @@ int launch(const T* sums, const T* counts, int k, int f, const float* C, int64_t
   if (blocks < 1) blocks = 1;
   double* part = reinterpret_cast<double*>(ws);
   unsigned* arrived = reinterpret_cast<unsigned*>(part + FIN_MAX_BLOCKS);
-  hipLaunchKernelGGL(km_finalize<T>, dim3((unsigned)blocks), dim3(256), 0, s, sums, counts, k, f, C, ldc, newC,
+  hipLaunchKernelGGL((km_finalize<T, TC>), dim3((unsigned)blocks), dim3(256), 0, s, sums, counts, k, f, C, ldc, newC,
                      shift, part, arrived);
   return ha_launch_status();
 }
@@ -79,12 +80,20 @@ HA_EXPORT int ha_km_finalize(const double* packed, int k, int f, const float* C,
                              double* shift, void* ws, void* stream) {
   if (k <= 0 || f <= 0 || ldc < f || (int64_t)k * f >= ((int64_t)1 << 31)) return HA_BAD_ARG;
   const int64_t kf = (int64_t)k * f;
-  return launch<double>(packed, packed + kf, k, f, C, ldc, newC, shift, ws, (hipStream_t)stream);
+  return launch<double, float>(packed, packed + kf, k, f, C, ldc, newC, shift, ws, (hipStream_t)stream);
 }
 
 // sums (k x f) and counts (k) as fp32 (single-process step)
 HA_EXPORT int ha_km_finalize_f32(const float* sums, const float* counts, int k, int f, const float* C, int64_t ldc,
                                  float* newC, double* shift, void* ws, void* stream) {
   if (k <= 0 || f <= 0 || ldc < f || (int64_t)k * f >= ((int64_t)1 << 31)) return HA_BAD_ARG;
-  return launch<float>(sums, counts, k, f, C, ldc, newC, shift, ws, (hipStream_t)stream);
+  return launch<float, float>(sums, counts, k, f, C, ldc, newC, shift, ws, (hipStream_t)stream);
+}
+
+// packed = [sums (k x f) | counts (k)], fp64; fp64 centroids in and out
+HA_EXPORT int ha_km_finalize_f64(const double* packed, int k, int f, const double* C, int64_t ldc, double* newC,
+                                 double* shift, void* ws, void* stream) {
+  if (k <= 0 || f <= 0 || ldc < f || (int64_t)k * f >= ((int64_t)1 << 31)) return HA_BAD_ARG;
+  const int64_t kf = (int64_t)k * f;
+  return launch<double, double>(packed, packed + kf, k, f, C, ldc, newC, shift, ws, (hipStream_t)stream);
 }

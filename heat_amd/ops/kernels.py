@@ -17,7 +17,7 @@ import torch.nn.functional as F
 
 from . import check, lib, stream_ptr, use_native
 
-__all__ = ["kmeans_finalize", "pack_blocks", "unpack_blocks", "pack_supported", "kmeans_assign", "kmeans_pack_points", "PackedPoints", "cdist_pack", "PackedRows", "kmeans_update", "moments", "merge_moments", "num_cus", "cdist", "cdist_f64", "lasso_epoch", "lasso_prepare", "LassoSweep", "gemm_f16x3",
+__all__ = ["kmeans_finalize", "pack_blocks", "unpack_blocks", "pack_supported", "kmeans_assign", "kmeans_pack_points", "PackedPoints", "cdist_pack", "PackedRows", "kmeans_update", "kmeans_assign_f64", "kmeans_update_f64", "moments", "merge_moments", "num_cus", "cdist", "cdist_f64", "lasso_epoch", "lasso_prepare", "LassoSweep", "gemm_f16x3",
            "split_planes", "gram_product", "gemm_f32_small", "knn_topk", "kmeans_step_small", "kmeans_lloyd_small", "lasso_gram", "lasso_cd", "argreduce_keys",
            "argreduce_decode", "argreduce_supported", "topk_rows", "gemm_f32", "gemm_h3", "h3_planes", "H3Planes",
            "gemm_h3_planes", "gemm64", "gemm_f64", "cholesky_upper", "tri_inv_upper", "householder_qr",
@@ -191,6 +191,14 @@ def kmeans_assign(X: torch.Tensor, C: torch.Tensor, want_mind: bool = True,
         if certified:
             kmeans_assign.last_rechecked = torch.zeros((), dtype=torch.int32, device=X.device)
         return labels, mind
+    if packed is None and not certified and _native64(X):
+        # float64 points: the fp64 MFMA kernel for every k and f (csrc/kmeans_f64.hip), no float32
+        # copy and no n x k matrix. Always native: for f <= 128 the old path was not float64-accurate,
+        # and for f > 128 addmm + min measured slower in every class (n = 4e6, f = 200, native / addmm
+        # ms: k = 8 3.18 / 3.67, k = 128 3.38 / 5.71, k = 1024 at n = 1e6 6.73 / 9.88;
+        # profiles/kmeans_f64_r09.jsonl)
+        labels, mind = kmeans_assign_f64(X, C, want_mind=want_mind)
+        return labels, (mind.float() if mind is not None else None)
     if packed is not None and use_native(X):
         if packed.n != n or packed.f != f:
             raise ValueError("packed points do not match X")
@@ -250,6 +258,38 @@ def kmeans_assign(X: torch.Tensor, C: torch.Tensor, want_mind: bool = True,
 
 
 kmeans_assign.last_rechecked = None
+
+
+def kmeans_assign_f64(X: torch.Tensor, C: torch.Tensor,
+                      want_mind: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Nearest centroid (squared L2, ties to the lowest index) of every row of the device float64
+    matrix X [n, f] among the rows of C [k, f]: (int32 labels, float64 min squared distance or None).
+    One fused kernel on the fp64 matrix cores with a running argmin in registers
+    (``csrc/kmeans_f64.hip``), any k and f; an operand is copied only if it is not 16-byte aligned
+    with an even row stride (:func:`_rows_f64_aligned`)."""
+    if X.ndim != 2 or C.ndim != 2 or X.shape[1] != C.shape[1] or C.shape[0] == 0:
+        raise ValueError("kmeans_assign_f64: X [n, f] and C [k, f] must be matrices with the same feature count")
+    if not _native64(X):
+        raise TypeError("kmeans_assign_f64 needs a device float64 X")
+    (n, f), k = X.shape, C.shape[0]
+    dev = X.device
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    mind = torch.empty(n, dtype=torch.float64, device=dev) if want_mind else None
+    if n == 0:
+        return labels, mind
+    if f == 0:
+        labels.zero_()
+        return labels, (mind.zero_() if want_mind else None)
+    Xa = _rows_f64_aligned(X)
+    Ca = _rows_f64_aligned(C.to(device=dev, dtype=torch.float64))
+
+    def ld(t):   # a single row has no stride
+        return t.stride(0) if t.shape[0] > 1 else f + f % 2
+
+    ws = torch.empty(k + (n if want_mind else 0), dtype=torch.float64, device=dev)
+    check(lib().ha_km_assign_f64(_ptr(Xa), n, f, ld(Xa), _ptr(Ca), k, ld(Ca), _ptr(ws), _ptr(labels), _ptr(mind),
+                                 ctypes.c_void_p(stream_ptr(dev))), "ha_km_assign_f64")
+    return labels, mind
 
 
 def _lex_key(d: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
@@ -433,8 +473,11 @@ def knn_topk(Q: torch.Tensor, T: torch.Tensor, k: int, packed: Optional[PackedPo
 
 
 def kmeans_update(X: torch.Tensor, labels: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Per-cluster feature sums [k, f] and counts [k] (float32) of the rows of X."""
+    """Per-cluster feature sums [k, f] and counts [k] of the rows of X: float32, or float64 for
+    device float64 points (:func:`kmeans_update_f64`)."""
     n, f = X.shape
+    if _native64(X) and (n == 0 or f == 0 or lib().ha_km_update_f64_workspace(n, k, f) >= 0):
+        return kmeans_update_f64(X, labels, k)
     if use_native(X) and X.dtype == torch.float32:
         L = lib()
         ncu = num_cus(X.device)
@@ -453,6 +496,37 @@ def kmeans_update(X: torch.Tensor, labels: torch.Tensor, k: int) -> Tuple[torch.
     sums = torch.zeros((k, f), dtype=X.dtype if X.is_floating_point() else torch.float32, device=X.device)
     sums.index_add_(0, lab, X.to(sums.dtype))
     counts = torch.bincount(lab, minlength=k).to(sums.dtype)
+    return sums, counts
+
+
+def kmeans_update_f64(X: torch.Tensor, labels: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-cluster feature sums [k, f] and counts [k], float64, of the rows of the device float64
+    matrix X (``csrc/kmeans.hip: ha_km_update_f64``): the counting-sort order of the float32 update,
+    fixed 256-position ranges summed sequentially and added in range order - no atomics, two calls
+    give the same bits. Labels outside [0, k) are ignored. Both results are views of one
+    [sums | counts] buffer, the layout :func:`kmeans_finalize` and the all-reduce take."""
+    if X.ndim != 2 or k <= 0:
+        raise ValueError("kmeans_update_f64: X must be a matrix and k positive")
+    if not _native64(X):
+        raise TypeError("kmeans_update_f64 needs a device float64 X")
+    n, f = X.shape
+    packed = torch.empty(k * f + k, dtype=torch.float64, device=X.device)
+    sums, counts = packed[:k * f].view(k, f), packed[k * f:]
+    if n == 0 or f == 0:
+        packed.zero_()
+        if f == 0 and n:
+            lab = labels.reshape(-1).to(torch.int64)
+            counts.copy_(torch.bincount(lab[(lab >= 0) & (lab < k)], minlength=k))
+        return sums, counts
+    L = lib()
+    wsize = L.ha_km_update_f64_workspace(n, k, f)
+    if wsize < 0:
+        raise ValueError("kmeans_update_f64: k = {} or n = {} beyond the kernel's range".format(k, n))
+    Xc = X if X.stride(1) == 1 and X.data_ptr() % 8 == 0 and (n == 1 or X.stride(0) >= f) else X.contiguous()
+    lab = labels.reshape(-1).to(torch.int32).contiguous()
+    ws = torch.empty(wsize, dtype=torch.int32, device=X.device)
+    check(L.ha_km_update_f64(_ptr(Xc), n, f, Xc.stride(0) if n > 1 else f, _ptr(lab), k, _ptr(sums), _ptr(counts),
+                             _ptr(ws), ctypes.c_void_p(stream_ptr(X.device))), "ha_km_update_f64")
     return sums, counts
 
 
@@ -2261,9 +2335,27 @@ def kmeans_finalize(packed: Optional[torch.Tensor], C: torch.Tensor, sums: Optio
     """Lloyd epilogue (``csrc/kmeans_finalize.hip``): from ``packed = [sums (k*f) | counts (k)]``
     (fp64; or fp32 ``sums`` [k, f] and ``counts`` [k] with ``packed=None``) and the current
     centroids C (float32, k x f) return (new centroids, squared shift as a 0-d fp64 tensor); empty
-    clusters keep their centroid. One launch on the GPU."""
+    clusters keep their centroid. One launch on the GPU. float64 C: float64 new centroids from fp64
+    sums and counts (``ha_km_finalize_f64``; unpacked ones are read in place where they are the two
+    views :func:`kmeans_update_f64` returns)."""
     k, f = C.shape
     dev_in = packed if packed is not None else sums
+    if dev_in.is_cuda and C.dtype == torch.float64 and 0 < k * f < 2 ** 31 and use_native(C):
+        if packed is not None:
+            pk = packed.double().contiguous()
+        elif (sums.dtype == counts.dtype == torch.float64 and sums.is_contiguous() and counts.is_contiguous()
+              and counts.data_ptr() == sums.data_ptr() + 8 * k * f
+              and sums.untyped_storage().data_ptr() == counts.untyped_storage().data_ptr()):
+            pk = sums
+        else:
+            pk = torch.cat([sums.reshape(-1).double(), counts.double()])
+        Cc = C if C.stride(-1) == 1 else C.contiguous()
+        newC = torch.empty((k, f), dtype=torch.float64, device=C.device)
+        shift = torch.empty((), dtype=torch.float64, device=C.device)
+        check(lib().ha_km_finalize_f64(_ptr(pk), k, f, _ptr(Cc), Cc.stride(0) if k > 1 else f, _ptr(newC),
+                                       _ptr(shift), _ptr(_finalize_ws(C.device)),
+                                       ctypes.c_void_p(stream_ptr(C.device))), "ha_km_finalize_f64")
+        return newC, shift
     if dev_in.is_cuda and C.dtype == torch.float32 and k * f < 2 ** 31 and use_native(C) and \
             hasattr(lib(), "ha_km_finalize_f32"):
         Cc = C if C.stride(-1) == 1 else C.contiguous()
