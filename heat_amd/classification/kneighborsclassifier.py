@@ -119,21 +119,26 @@ class KNeighborsClassifier(ClassificationMixin, BaseEstimator):
         q = x.larray if x.larray.is_floating_point() else x.larray.float()
         train = self.x
         tl = train.larray.to(q.dtype)
+        # device float64 queries and training data stay float64 (ops.knn_topk's fused fp64 kernel);
+        # everything else is searched in float32
+        wd = torch.float64 if (q.is_cuda and q.dtype == torch.float64 and train.larray.dtype == torch.float64
+                               and ops.use_native(q)) else torch.float32
+        q = q.to(wd)
         ylab = self.y.larray.to(torch.float32)
         nq = q.shape[0]
-        best_d = torch.full((nq, k), float("inf"), dtype=torch.float32, device=q.device)
+        best_d = torch.full((nq, k), float("inf"), dtype=wd, device=q.device)
         best_i = torch.full((nq, k), torch.iinfo(torch.int64).max, dtype=torch.int64, device=q.device)
         best_y = torch.zeros((nq, k, ylab.shape[1]), dtype=torch.float32, device=q.device)
         if train.is_distributed():
             if ylab.shape[0] != tl.shape[0]:
                 raise ValueError("training rows ({}) and local labels ({}) are not aligned".format(
                     tl.shape[0], ylab.shape[0]))
-            packed = torch.cat([tl.float(), ylab], dim=1)
+            packed = torch.cat([tl.to(wd), ylab.to(wd)], dim=1)
             counts = train.split_counts()
             starts = [sum(counts[:r]) for r in range(len(counts))]
 
             def visit(block: torch.Tensor, src: int):
-                _merge(block[:, : tl.shape[1]], block[:, tl.shape[1]:], starts[src])
+                _merge(block[:, : tl.shape[1]], block[:, tl.shape[1]:].float(), starts[src])
 
         def _merge(tb: torch.Tensor, yb: torch.Tensor, row0: int):
             nonlocal best_d, best_i, best_y
@@ -141,7 +146,7 @@ class KNeighborsClassifier(ClassificationMixin, BaseEstimator):
                 return
             # fused distance + running top-k kernel (no nq x nt matrix); exact distances of the picks
             kk = min(k, tb.shape[0])
-            dv, di = ops.knn_topk(q.float(), tb.float(), kk)
+            dv, di = ops.knn_topk(q, tb.to(wd), kk)
             cand_d = torch.cat([best_d, dv], dim=1)
             cand_i = torch.cat([best_i, di.to(torch.int64) + row0], dim=1)
             cand_y = torch.cat([best_y, yb[di.reshape(-1)].reshape(nq, kk, -1)], dim=1)
@@ -153,7 +158,7 @@ class KNeighborsClassifier(ClassificationMixin, BaseEstimator):
         if train.is_distributed():
             ring_pass(packed, visit, train.comm, counts)
         else:
-            _merge(tl.float(), ylab, 0)
+            _merge(tl.to(wd), ylab, 0)
         votes = best_y.sum(1)
         lab = torch.argmax(votes, dim=1)
         self.classes_ = DNDarray(lab, (x.gshape[0],), ht.int64, x.split, x.device, x.comm, x.balanced)

@@ -420,14 +420,18 @@ def knn_topk(Q: torch.Tensor, T: torch.Tensor, k: int, packed: Optional[PackedPo
     per point in registers, ``csrc/kmeans_f16x3.hip: h3_topk_p``), no nq x nt distance matrix;
     for k <= 8 (and enough queries to fill the GPU) the certified one-term pass first
     (``h1_topk``, :func:`_knn_certified`). The selected neighbours' distances are then recomputed
-    exactly (difference form) and re-sorted (``exact_distances``). Otherwise: distance tiles +
-    torch.topk, in query blocks."""
+    exactly (difference form) and re-sorted (``exact_distances``). Device float64 Q and T with
+    k <= 16: float64 distances from the fused fp64 kernel (``cdist_f64(..., topk=k)``,
+    ``csrc/knn_f64.hip``), always exact. Otherwise: distance tiles + torch.topk, in query blocks."""
     nq, f = Q.shape
     nt = T.shape[0]
     dev = Q.device
     if nq == 0 or nt == 0 or k <= 0:
         return (torch.full((nq, max(k, 0)), float("inf"), device=dev),
                 torch.full((nq, max(k, 0)), -1, dtype=torch.int64, device=dev))
+    if _native64(Q) and _native64(T) and Q.device == T.device and k <= _KNN_F64_MAX_K:
+        # float64 stays float64: the fused fp64 kernel, always with exact distances
+        return cdist_f64(Q, T, "sqeuclidean", topk=k)
     if use_native(Q) and Q.dtype == torch.float32 and T.dtype == torch.float32 and k <= 16 \
             and lib().ha_h3_fpad(f) > 0 and nt < 2 ** 31 - 256:
         L = lib()
@@ -807,8 +811,51 @@ def _rows_f64_aligned(X: torch.Tensor) -> torch.Tensor:
     return P[:, :f]
 
 
+_KNN_F64_MAX_K = 16   # csrc/knn_f64.hip: list length of the fused float64 kernel
+
+
+def _knn_f64(X: torch.Tensor, Y: torch.Tensor, k: int, root: bool, splits: Optional[int]):
+    """The k <= 16 nearest rows of Y for every row of X, both device float64 (``csrc/knn_f64.hip``):
+    (distances [m, k] float64 ascending, int64 indices [m, k]), (+inf, -1) behind Y's last row. One
+    fused pass (fp64 MFMA scores, per-query top-k lists in LDS) writes ``splits`` partial lists per
+    query, one rescoring launch merges them by exact difference-form distances. With few query
+    tiles Y's 128-row tiles are divided over ``splits`` workgroup columns (>= 4 tiles each,
+    splits * k <= 64) until two workgroups per CU are resident."""
+    (m, f), n = X.shape, Y.shape[0]
+    dev = X.device
+    dist = torch.full((m, k), float("inf"), dtype=torch.float64, device=dev)
+    idx = torch.full((m, k), -1, dtype=torch.int64, device=dev)
+    if m == 0 or n == 0:
+        return dist, idx
+    if f == 0:   # every distance is 0: the first rows of Y
+        kk = min(k, n)
+        dist[:, :kk] = 0.0
+        idx[:, :kk] = torch.arange(kk, device=dev)
+        return dist, idx
+    Xa = _rows_f64_aligned(X)
+    Ya = Xa if Y is X else _rows_f64_aligned(Y)
+
+    def ld(t):   # a single row has no stride
+        return t.stride(0) if t.shape[0] > 1 else f + f % 2
+
+    qblocks, tiles = (m + 127) // 128, (n + 127) // 128
+    if splits is None:
+        splits = min(tiles // 4, (2 * num_cus(dev) + qblocks - 1) // qblocks)
+    splits = max(1, min(int(splits), 64 // k, tiles))
+    L, st = lib(), ctypes.c_void_p(stream_ptr(dev))
+    ws = torch.empty(n, dtype=torch.float64, device=dev)
+    part_s = torch.empty((splits, m, k), dtype=torch.float64, device=dev)
+    part_i = torch.empty((splits, m, k), dtype=torch.int32, device=dev)
+    check(L.ha_knn_f64(_ptr(Xa), m, f, ld(Xa), _ptr(Ya), n, ld(Ya), k, splits, _ptr(ws), _ptr(part_s), _ptr(part_i),
+                       st), "ha_knn_f64")
+    check(L.ha_knn_rescore_f64(_ptr(Xa), ld(Xa), _ptr(Ya), ld(Ya), n, m, f, _ptr(part_i), splits, k, k, _ptr(dist),
+                               _ptr(idx), st), "ha_knn_rescore_f64")
+    return (torch.sqrt(dist) if root else dist), idx
+
+
 def cdist_f64(X: torch.Tensor, Y: torch.Tensor, metric: str = "euclidean", sigma: float = 1.0,
-              out: Optional[torch.Tensor] = None, exact: bool = False, symmetric: bool = False) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, exact: bool = False, symmetric: bool = False,
+              topk: Optional[int] = None, _splits: Optional[int] = None):
     """float64 pairwise distances between the rows of the device float64 matrices X [m, f] and
     Y [n, f] (``csrc/cdist_f64.hip``), written once by the tile kernel's own epilogue.
 
@@ -818,13 +865,25 @@ def cdist_f64(X: torch.Tensor, Y: torch.Tensor, metric: str = "euclidean", sigma
     without a copy; every pair is summed over the features in index order, so an entry does not
     depend on the shapes or the tile it falls in. ``symmetric`` (``Y is X``, difference kernel):
     tiles on or above the diagonal computed once and mirrored. ``out``: a float64 row-contiguous
-    matrix of at least m x n whose first m x n entries are written; it is returned as given."""
+    matrix of at least m x n whose first m x n entries are written; it is returned as given.
+
+    ``topk=k`` (1 <= k <= 16, ``"sqeuclidean"`` or ``"euclidean"``, no ``out`` / ``symmetric``): instead
+    of the matrix, ``(dist [m, k] float64 ascending, idx [m, k] int64)`` of the k nearest rows of Y
+    from the fused kernel of ``csrc/knn_f64.hip`` (:func:`_knn_f64`): selected by the expansion
+    scores, equal scores by index, the distances exact (difference form); (+inf, -1) where n < k.
+    ``_splits`` overrides the number of workgroup columns Y is divided over."""
     if X.ndim != 2 or Y.ndim != 2 or X.shape[1] != Y.shape[1]:
         raise ValueError("cdist_f64: X [m, f] and Y [n, f] must be matrices with the same feature count")
     if metric not in _CDIST_MODES:
         raise ValueError("unknown metric {}".format(metric))
     if not (_native64(X) and _native64(Y)) or X.device != Y.device:
         raise TypeError("cdist_f64 needs float64 tensors on one device")
+    if topk is not None:
+        if metric not in ("sqeuclidean", "euclidean") or out is not None or symmetric:
+            raise ValueError("cdist_f64: topk needs metric 'sqeuclidean' or 'euclidean' and neither out nor symmetric")
+        if not isinstance(topk, int) or not 1 <= topk <= _KNN_F64_MAX_K:
+            raise ValueError("cdist_f64: topk must be an integer in [1, {}], got {}".format(_KNN_F64_MAX_K, topk))
+        return _knn_f64(X, Y, topk, metric == "euclidean", _splits)
     (m, f), n = X.shape, Y.shape[0]
     if out is None:
         out = torch.empty((m, n), dtype=torch.float64, device=X.device)

@@ -305,12 +305,14 @@ def cdist_topk(X: DNDarray, Y: Optional[DNDarray] = None, k: int = 1):
     distance matrix: ``(distances, indices)``, both (m, k), ascending, split like ``X``; the
     indices are global row numbers of ``Y``. Equal distances are ordered by index, so the result
     does not depend on the number of ranks (on the fused fp32 device kernel: among the candidates it
-    returns - of exactly duplicated rows of ``Y`` at the k-th place it keeps one).
+    returns - of exactly duplicated rows of ``Y`` at the k-th place it keeps one; the fused float64
+    kernel scores exactly duplicated rows alike and keeps them all, in index order).
 
     The fused reduction the reference leaves to the caller (it materialises ``cdist`` and runs a
     distributed ``topk``, ``heat/classification/kneighborsclassifier.py:117-160``): device fp32 runs
-    the fused MFMA distance + register top-k kernel (``ops.knn_topk``) per ``Y`` block, other inputs
-    exact distance tiles in query blocks; a split ``Y`` circulates around the ring
+    the fused MFMA distance + register top-k kernel (``ops.knn_topk``) per ``Y`` block, device fp64
+    with k <= 16 its fp64 sibling (fp64 MFMA scores + per-query lists in LDS), other inputs exact
+    distance tiles in query blocks; a split ``Y`` circulates around the ring
     (``parallel.ring_pass``) and every rank keeps a running top-k of its own queries."""
     if Y is None:
         Y = X
@@ -337,7 +339,13 @@ def cdist_topk(X: DNDarray, Y: Optional[DNDarray] = None, k: int = 1):
 
     def block_topk(block: torch.Tensor):
         kk = min(k, block.shape[0])
-        if tt == torch.float32 and ops.use_native(x):
+        # float64: the fused fp64 kernel for kk <= 16 (ops.cdist_f64(..., topk=kk)), tiles beyond. Its
+        # split columns are capped at 64 // kk, so at most two query tiles with kk > 8 leave the GPU
+        # idle against a long block and go to the tiles too: nq = 256, 1e6 rows, kk = 16: 23.7 ms fused
+        # / 23.3 ms tiles at f = 18, 48.3 / 38.2 at f = 128, while kk = 1 is 1.3 / 23.0 and 3.1 / 37.5 ms
+        # (profiles/knn_f64_r10.jsonl)
+        few = kk > 8 and nq <= 256 and block.shape[0] >= 1 << 19
+        if ops.use_native(x) and (tt == torch.float32 or (kk <= 16 and block.is_cuda and not few)):
             dv, di = ops.knn_topk(x, block, kk)
             return dv.to(tt), di.to(torch.int64)
         step = max(1, (1 << 24) // max(block.shape[0], 1))  # <= 16M entries per tile (x3 tensors)
