@@ -178,11 +178,53 @@ def std(x: DNDarray, axis=None, ddof: int = 0, **kwargs) -> DNDarray:
     return var(x, axis, ddof, _final="std", **kwargs)
 
 
+def _allmerge4(comm, n, mu, m2, m3, m4):
+    """Pebay merge of every rank's (n, mean, M2, M3, M4) partials (fp64), split like
+    :func:`_allmerge`. Small outputs: ONE all-gather of the packed quintuples, merged in rank order.
+    Large outputs: all-reduce [n, n mean] -> global mean, shift each rank's central sums to it, then
+    ONE all-reduce of the three sums."""
+    shape = n.shape
+    q = [v.reshape(-1) for v in (n, mu, m2, m3, m4)]
+    if n.numel() <= _ALLGATHER_MERGE_MAX:
+        allp = comm.allgather_tensor(torch.stack(q).unsqueeze(0).contiguous(), 0)   # [p, 5, out]
+        return tuple(v.reshape(shape) for v in ops.merge_moments4(*allp.unbind(1), 0))
+    s = torch.stack([q[0], q[0] * q[1]])
+    comm.Allreduce(MPI.IN_PLACE, s, MPI.SUM)
+    N = s[0]
+    MU = s[1] / torch.where(N > 0, N, torch.ones_like(N))
+    d = q[1] - MU
+    d2 = d * d
+    M = torch.stack([q[2] + q[0] * d2, q[3] + 3.0 * d * q[2] + q[0] * d2 * d,
+                     q[4] + 4.0 * d * q[3] + 6.0 * d2 * q[2] + q[0] * d2 * d2])
+    comm.Allreduce(MPI.IN_PLACE, M, MPI.SUM)
+    return tuple(v.reshape(shape) for v in (N, MU, M[0], M[1], M[2]))
+
+
+def _central_moment_sums_device(x: DNDarray, axis, powers):
+    """:func:`_central_moment_sums` for a device float32 / float64 block: ONE pass over it
+    (``ops.moments4``), and a merge of the ranks' quintuples where the split axis is reduced."""
+    n, mu, m2, m3, m4 = ops.moments4(x.larray, axis)
+    merge = x.is_distributed() and (axis is None or axis == x.split)
+    if merge:
+        n, mu, m2, m3, m4 = _allmerge4(x.comm, n, mu, m2, m3, m4)
+    sums = torch.stack([{2: m2, 3: m3, 4: m4}[k] for k in powers])
+    if axis is None:
+        return float(x.gnumel), sums, (), None, True
+    gshape = tuple(s for i, s in enumerate(x.gshape) if i != axis)
+    split, bal = None, True
+    if not merge and x.split is not None and x.split != axis:
+        split = x.split if x.split < axis else x.split - 1
+        bal = x.balanced
+    return float(x.gshape[axis]), sums, gshape, split, bal
+
+
 def _central_moment_sums(x: DNDarray, axis, powers=(2, 3, 4)):
     """Two-pass central moments: global mean, then sums of (x - mean)^k (one all-reduce)."""
     if axis is not None and (not isinstance(axis, (int, np.integer)) or isinstance(axis, bool)):
         raise TypeError("axis must be None or an int, got {}".format(type(axis)))
     sanitize_axis(x.gshape, axis)
+    if x.larray.is_cuda and x.larray.dtype in (torch.float32, torch.float64):
+        return _central_moment_sums_device(x, sanitize_axis(x.gshape, axis), powers)
     mu = mean(x, axis)
     t = x.larray.double()
     axis_s = sanitize_axis(x.gshape, axis)
@@ -206,7 +248,8 @@ def _central_moment_sums(x: DNDarray, axis, powers=(2, 3, 4)):
 
 
 def skew(x: DNDarray, axis: Optional[int] = None, unbiased: bool = True) -> DNDarray:
-    """Sample skewness (Fisher-Pearson; bias-corrected when ``unbiased``)."""
+    """Sample skewness (Fisher-Pearson; bias-corrected when ``unbiased``). Device float32 and float64
+    arrays take their central moments from one fused pass (``ops.moments4``)."""
     n, s, gshape, split, bal = _central_moment_sums(x, axis, (2, 3))
     m2, m3 = s[0] / n, s[1] / n
     g1 = m3 / m2 ** 1.5
@@ -216,7 +259,8 @@ def skew(x: DNDarray, axis: Optional[int] = None, unbiased: bool = True) -> DNDa
 
 
 def kurtosis(x: DNDarray, axis: Optional[int] = None, unbiased: bool = True, Fischer: bool = True) -> DNDarray:
-    """Kurtosis (Fisher: excess, Pearson otherwise; bias-corrected when ``unbiased``)."""
+    """Kurtosis (Fisher: excess, Pearson otherwise; bias-corrected when ``unbiased``). Device float32
+    and float64 arrays take their central moments from one fused pass (``ops.moments4``)."""
     n, s, gshape, split, bal = _central_moment_sums(x, axis, (2, 4))
     m2, m4 = s[0] / n, s[1] / n
     g2 = m4 / m2 ** 2

@@ -39,3 +39,28 @@ __device__ __forceinline__ void ha_store_wt(double* p, double v) {
   __hip_atomic_store((ha_gu64*)(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
                      __HIP_MEMORY_SCOPE_AGENT);
 }
+
+// The ticket of that hand-off (moments.hip, moments4.hip). This block's partials are stored
+// write-through (ha_store_wt) by the threads that own them; each of those waves drained them
+// (s_waitcnt vmcnt(0)) before the barrier here. Lane 0 takes a ticket on the per-output arrival
+// counter (agent-scope atomic, no release fence); true in every thread of the block that arrived
+// last, after ONE agent acquire, which also resets the counter for the next launch on this
+// workspace.
+__device__ __forceinline__ bool mom_last_arrival(unsigned* __restrict__ cnt, unsigned expected) {
+  __shared__ bool last;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned t = __hip_atomic_fetch_add((ha_gu32*)(cnt), 1u, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_AGENT);
+    const bool l = t == expected - 1;
+    if (l) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __hip_atomic_store((ha_gu32*)(cnt), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    last = l;
+  }
+  __syncthreads();
+  return last;
+}

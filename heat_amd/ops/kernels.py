@@ -17,7 +17,7 @@ import torch.nn.functional as F
 
 from . import check, lib, stream_ptr, use_native
 
-__all__ = ["kmeans_finalize", "pack_blocks", "unpack_blocks", "pack_supported", "kmeans_assign", "kmeans_pack_points", "PackedPoints", "cdist_pack", "PackedRows", "kmeans_update", "kmeans_assign_f64", "kmeans_update_f64", "moments", "merge_moments", "num_cus", "cdist", "cdist_f64", "lasso_epoch", "lasso_prepare", "LassoSweep", "gemm_f16x3",
+__all__ = ["kmeans_finalize", "pack_blocks", "unpack_blocks", "pack_supported", "kmeans_assign", "kmeans_pack_points", "PackedPoints", "cdist_pack", "PackedRows", "kmeans_update", "kmeans_assign_f64", "kmeans_update_f64", "moments", "merge_moments", "moments4", "merge_moments4", "num_cus", "cdist", "cdist_f64", "lasso_epoch", "lasso_prepare", "LassoSweep", "gemm_f16x3",
            "split_planes", "gram_product", "gemm_f32_small", "knn_topk", "kmeans_step_small", "kmeans_lloyd_small", "lasso_gram", "lasso_cd", "argreduce_keys",
            "argreduce_decode", "argreduce_supported", "topk_rows", "gemm_f32", "gemm_h3", "h3_planes", "H3Planes",
            "gemm_h3_planes", "gemm64", "gemm_f64", "cholesky_upper", "tri_inv_upper", "householder_qr",
@@ -668,6 +668,110 @@ def moments(x: torch.Tensor, axis: Optional[int] = None, final: Optional[str] = 
         return mean
     v = m2 / (n - ddof)
     return v.sqrt() if final == "std" else v
+
+
+def merge_moments4(n: torch.Tensor, mean: torch.Tensor, m2: torch.Tensor, m3: torch.Tensor, m4: torch.Tensor,
+                   dim: int):
+    """Pebay merge of (count, mean, M2, M3, M4) partials along ``dim`` (fp64), all partials at once:
+    every partial's central sums are shifted to the merged mean, d = mean_i - mean, and added,
+    ``M3 = sum m3_i + 3 d m2_i + n_i d^3``, ``M4 = sum m4_i + 4 d m3_i + 6 d^2 m2_i + n_i d^4``.
+    Empty partials (n = 0, sums 0) add nothing."""
+    N = n.sum(dim)
+    safe = torch.where(N > 0, N, torch.ones_like(N))
+    mu = (n * mean).sum(dim) / safe
+    d = mean - mu.unsqueeze(dim)
+    d2 = d * d
+    M2 = (m2 + n * d2).sum(dim)
+    M3 = (m3 + 3.0 * d * m2 + n * d2 * d).sum(dim)
+    M4 = (m4 + 4.0 * d * m3 + 6.0 * d2 * m2 + n * d2 * d2).sum(dim)
+    return N, mu, M2, M3, M4
+
+
+def _moments4_native(x: torch.Tensor, axis):
+    """One launch (``csrc/moments4.hip``): the five planes (n, mean, M2, M3, M4) of the outputs."""
+    L = lib()
+    s = ctypes.c_void_p(stream_ptr(x.device))
+    ncu = num_cus(x.device)
+    dt = 0 if x.dtype == torch.float32 else 1
+
+    def workspace(query, nout, nchunks):
+        pd, nc = ctypes.c_int64(), ctypes.c_int64()
+        query(nout, nchunks, ctypes.byref(pd), ctypes.byref(nc))
+        part = torch.empty(pd.value, dtype=torch.float64, device=x.device) if pd.value else None
+        return part, (_mom_counters(x.device, nc.value) if nc.value else None)
+
+    def rows(t, nrows, red, nchunks, out_shape):
+        part, cnt = workspace(L.ha_moments4_rows_workspace, nrows, nchunks)
+        out = torch.empty((5,) + tuple(out_shape), dtype=torch.float64, device=x.device)
+        check(L.ha_moments4_rows(_ptr(t), dt, nrows, red, red, nchunks, _ptr(part), _ptr(out), _ptr(cnt), s),
+              "ha_moments4_rows")
+        return tuple(out.unbind(0))
+
+    if axis is None:
+        flat = x.reshape(-1)
+        if not flat.is_contiguous():
+            flat = flat.contiguous()
+        numel = flat.numel()
+        # 8 blocks per CU: 6 fp64 operations per element want more waves over the loads than mean's 4
+        return rows(flat, 1, numel, max(1, min(8 * ncu, (numel + 16383) // 16384)), ())
+    if not x.is_contiguous():
+        x = x.contiguous()
+    shape = list(x.shape)
+    red = shape[axis]
+    outer = 1
+    for d in shape[:axis]:
+        outer *= d
+    inner = 1
+    for d in shape[axis + 1:]:
+        inner *= d
+    out_shape = shape[:axis] + shape[axis + 1:]
+    if inner == 1:
+        # a wave per row up to 16K elements; longer rows are split over at least two blocks
+        nchunks = max(1, min((2 * 8 * ncu + outer - 1) // max(outer, 1), (red + 4095) // 4096))
+        if red > 16384:
+            nchunks = max(nchunks, 2)
+        return rows(x, outer, red, nchunks, out_shape)
+    if outer == 1:
+        ncols = inner
+        epv = 16 // x.element_size()
+        vec = ncols % epv == 0 and x.data_ptr() % 16 == 0
+        col_blocks = ((ncols // epv if vec else ncols) + 255) // 256
+        # 4 row chunks per CU (4 waves per SIMD over 8 rows in flight each) of at least 512 rows,
+        # so that the 16 rows every chunk reads twice for its shift stay under 3% of the traffic
+        nchunks = max(1, min(65535, (4 * ncu + col_blocks - 1) // col_blocks, (red + 511) // 512))
+        part, cnt = workspace(L.ha_moments4_cols_workspace, ncols, nchunks)
+        out = torch.empty((5,) + tuple(out_shape), dtype=torch.float64, device=x.device)
+        check(L.ha_moments4_cols(_ptr(x), dt, red, ncols, ncols, nchunks, _ptr(part), _ptr(out), _ptr(cnt), s),
+              "ha_moments4_cols")
+        return tuple(out.unbind(0))
+    y = x.movedim(axis, -1).contiguous()
+    return _moments4_native(y, y.dim() - 1)
+
+
+def moments4(x: torch.Tensor, axis: Optional[int] = None):
+    """(count, mean, M2, M3, M4) over ``axis`` (None = all) as float64 tensors shaped like the reduced
+    output, ``Mk = sum (x - mean)^k``: the central sums of variance, skewness and kurtosis.
+
+    Device float32 / float64 tensors: ONE kernel launch - one HBM pass with 16-byte loads, fp64
+    shifted power sums and the chunk merge fused into each output's last block (``moments4.hip``).
+    Everything else: a two-pass fp64 torch expression."""
+    if use_native(x) and x.dtype in (torch.float32, torch.float64) and x.numel() > 0:
+        if axis is not None:
+            axis = axis % x.dim()
+        return _moments4_native(x, axis)
+    xd = x.double()
+    if axis is None:
+        xd, axis = xd.reshape(-1), 0
+    count = xd.shape[axis]
+    n = torch.full([s for i, s in enumerate(xd.shape) if i != axis], float(count), dtype=torch.float64,
+                   device=x.device)
+    if count == 0:
+        z = torch.zeros_like(n)
+        return n, z, z.clone(), z.clone(), z.clone()
+    mean = xd.mean(dim=axis)
+    d = xd - mean.unsqueeze(axis)
+    d2 = d * d
+    return n, mean, d2.sum(dim=axis), (d2 * d).sum(dim=axis), (d2 * d2).sum(dim=axis)
 
 
 # --------------------------------------------------------------------------------------------- cdist
