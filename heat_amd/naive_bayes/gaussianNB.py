@@ -6,19 +6,33 @@ Gaussian Naive Bayes (reference ``heat/naive_bayes/gaussianNB.py``: ``GaussianNB
 All classes are updated together: one segmented pass (per-class weighted count / sum / squared
 deviation via ``index_add``) and ONE all-reduce of the packed per-class moments, then the Chan
 merge with the previous state (the reference loops over classes with a distributed mean/var each).
+
+Device float32 / float64 data with up to 64 classes runs on the fused kernels of ``ops/csrc/gnb.hip``:
+``fit`` is one pass (``ops.class_moments``) plus, when split, one exchange of the packed triples;
+``predict`` / ``predict_log_proba`` / ``predict_proba`` are one pass with the argmax or the logsumexp in
+registers (``ops.gnb_jll``). ``HEAT_GNB_NATIVE=0`` keeps the torch expressions for A/B runs.
 """
 from __future__ import annotations
 
+import os
 from typing import Optional, Tuple, Union
 
 import torch
 
 from .. import core as ht
+from .. import ops
 from ..core.base import BaseEstimator, ClassificationMixin
-from ..core.communication import MPI
+from ..core.communication import MPI, PATH_COUNTS
 from ..core.dndarray import DNDarray
 
 __all__ = ["GaussianNB"]
+
+
+def _native(X: torch.Tensor, k: int) -> bool:
+    """Whether local data ``X`` with ``k`` classes takes the fused kernels (read per call: A/B runs flip
+    ``HEAT_GNB_NATIVE`` inside one process)."""
+    return (os.environ.get("HEAT_GNB_NATIVE", "1") != "0" and X.dtype in (torch.float32, torch.float64)
+            and 0 < k <= ops.GNB_MAX_CLASSES and X.dim() == 2 and 0 < X.shape[1] < 2 ** 31 and ops.use_native(X))
 
 
 class GaussianNB(ClassificationMixin, BaseEstimator):
@@ -65,6 +79,29 @@ class GaussianNB(ClassificationMixin, BaseEstimator):
             r = like.comm.rank
             return full[displs[r]: displs[r] + counts[r]]
         return full
+
+    def _class_moments_torch(self, x: DNDarray, X: torch.Tensor, idx: torch.Tensor, k: int,
+                             sample_weight: Optional[DNDarray]):
+        """Global per-class (count, mean, M2) by two ``index_add_`` passes over a float64 copy and, when
+        split, two all-reduces (host tensors, more than 64 classes, ``HEAT_GNB_NATIVE=0``)."""
+        f = X.shape[1]
+        w = self._local_rows(sample_weight, x).to(torch.float64) if sample_weight is not None else \
+            torch.ones(X.shape[0], dtype=torch.float64, device=X.device)
+        Xd = X.to(torch.float64)
+        # pass 1: weighted counts and sums -> means
+        cnt = torch.zeros(k, dtype=torch.float64, device=X.device).index_add_(0, idx, w)
+        sums = torch.zeros(k, f, dtype=torch.float64, device=X.device).index_add_(0, idx, Xd * w.unsqueeze(1))
+        packed = torch.cat([cnt, sums.reshape(-1)])
+        if x.is_distributed():
+            x.comm.Allreduce(MPI.IN_PLACE, packed, MPI.SUM)
+        cnt, sums = packed[:k], packed[k:].reshape(k, f)
+        mu = sums / cnt.clamp(min=1e-300).unsqueeze(1)
+        # pass 2: weighted squared deviations
+        dev = (Xd - mu[idx]) ** 2 * w.unsqueeze(1)
+        m2 = torch.zeros(k, f, dtype=torch.float64, device=X.device).index_add_(0, idx, dev)
+        if x.is_distributed():
+            x.comm.Allreduce(MPI.IN_PLACE, m2, MPI.SUM)
+        return cnt, mu, m2
 
     def _partial_fit(self, x: DNDarray, y: DNDarray, classes: Optional[DNDarray], _refit: bool,
                      sample_weight: Optional[DNDarray]) -> "GaussianNB":
@@ -128,22 +165,24 @@ class GaussianNB(ClassificationMixin, BaseEstimator):
                 torch.unique(yl[bad]).tolist() if yl.numel() else [], cl.tolist()))
         k = cl.numel()
         f = X.shape[1]
-        w = self._local_rows(sample_weight, x).to(torch.float64) if sample_weight is not None else \
-            torch.ones(X.shape[0], dtype=torch.float64, device=X.device)
-        Xd = X.to(torch.float64)
-        # pass 1: weighted counts and sums -> means
-        cnt = torch.zeros(k, dtype=torch.float64, device=X.device).index_add_(0, idx, w)
-        sums = torch.zeros(k, f, dtype=torch.float64, device=X.device).index_add_(0, idx, Xd * w.unsqueeze(1))
-        packed = torch.cat([cnt, sums.reshape(-1)])
-        if x.is_distributed():
-            x.comm.Allreduce(MPI.IN_PLACE, packed, MPI.SUM)
-        cnt, sums = packed[:k], packed[k:].reshape(k, f)
-        mu = sums / cnt.clamp(min=1e-300).unsqueeze(1)
-        # pass 2: weighted squared deviations
-        dev = (Xd - mu[idx]) ** 2 * w.unsqueeze(1)
-        m2 = torch.zeros(k, f, dtype=torch.float64, device=X.device).index_add_(0, idx, dev)
-        if x.is_distributed():
-            x.comm.Allreduce(MPI.IN_PLACE, m2, MPI.SUM)
+        if _native(X, k):
+            # one fused pass (csrc/gnb.hip) and, when split, ONE exchange of the ranks' packed triples
+            PATH_COUNTS["gnb_fit:native"] += 1
+            w = self._local_rows(sample_weight, x) if sample_weight is not None else None
+            if X.shape[0] > 0:
+                cnt, mu, m2 = ops.class_moments(X, idx, k, w)
+            else:
+                cnt = torch.zeros(k, dtype=torch.float64, device=X.device)
+                mu, m2 = (torch.zeros(k, f, dtype=torch.float64, device=X.device) for _ in range(2))
+            if x.is_distributed():
+                packed = torch.cat([cnt, mu.reshape(-1), m2.reshape(-1)]).unsqueeze(0)
+                allp = x.comm.allgather_tensor(packed, 0)                                  # [p, k + 2 k f]
+                n_r = allp[:, :k].unsqueeze(2)
+                mu_r, m2_r = allp[:, k:k + k * f].reshape(-1, k, f), allp[:, k + k * f:].reshape(-1, k, f)
+                cnt, mu, m2 = ops.merge_moments(n_r, mu_r, m2_r, 0)
+                cnt = cnt.reshape(k)
+        else:
+            cnt, mu, m2 = self._class_moments_torch(x, X, idx, k, sample_weight)
         # Chan merge with the previous state
         n_old = self.class_count_.larray.to(torch.float64)
         mu_old = self.theta_.larray.to(torch.float64)
@@ -163,9 +202,26 @@ class GaussianNB(ClassificationMixin, BaseEstimator):
         return self
 
     # ----------------------------------------------------------------- prediction
-    def _joint_log_likelihood(self, x: DNDarray) -> DNDarray:
+    def _fused_likelihood(self, x: DNDarray, out: str) -> Optional[torch.Tensor]:
+        """``ops.gnb_jll`` of ``x``'s local rows where the fused kernel serves them, else None."""
         if not isinstance(x, DNDarray):
             raise ValueError("input needs to be a ht.DNDarray, but was {}".format(type(x)))
+        X = x.larray if x.larray.is_floating_point() else x.larray.double()
+        k = self.theta_.larray.shape[0]
+        if not _native(X, k) or X.shape[1] != self.theta_.larray.shape[1]:
+            return None
+        PATH_COUNTS["gnb_predict:native"] += 1
+        if X.shape[0] == 0:
+            return torch.empty((0,) if out == "argmax" else (0, k), device=X.device,
+                               dtype=torch.int64 if out == "argmax" else X.dtype)
+        log_prior = torch.log(self.class_prior_.larray.to(device=X.device, dtype=X.dtype))
+        return ops.gnb_jll(X, self.theta_.larray, self.sigma_.larray, log_prior, out=out)
+
+    def _joint_log_likelihood(self, x: DNDarray) -> DNDarray:
+        jll = self._fused_likelihood(x, "jll")
+        if jll is not None:
+            return DNDarray(jll, (x.gshape[0], jll.shape[1]), ht.types.canonical_heat_type(jll.dtype), x.split,
+                            x.device, x.comm, x.balanced)
         X = x.larray if x.larray.is_floating_point() else x.larray.double()
         theta = self.theta_.larray.to(X.dtype)
         sigma = self.sigma_.larray.to(X.dtype)
@@ -191,12 +247,17 @@ class GaussianNB(ClassificationMixin, BaseEstimator):
         return out + a_max
 
     def predict(self, x: DNDarray) -> DNDarray:
-        jll = self._joint_log_likelihood(x)
-        idx = torch.argmax(jll.larray, dim=1)
+        idx = self._fused_likelihood(x, "argmax")
+        if idx is None:
+            idx = torch.argmax(self._joint_log_likelihood(x).larray, dim=1)
         lab = self.classes_.larray[idx]
         return DNDarray(lab, (x.gshape[0],), self.classes_.dtype, x.split, x.device, x.comm, x.balanced)
 
     def predict_log_proba(self, x: DNDarray) -> DNDarray:
+        lp = self._fused_likelihood(x, "log_proba")
+        if lp is not None:
+            return DNDarray(lp, (x.gshape[0], lp.shape[1]), ht.types.canonical_heat_type(lp.dtype), x.split, x.device,
+                            x.comm, x.balanced)
         jll = self._joint_log_likelihood(x)
         t = jll.larray
         norm = torch.logsumexp(t, dim=1, keepdim=True)

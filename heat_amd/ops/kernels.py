@@ -22,7 +22,7 @@ __all__ = ["kmeans_finalize", "pack_blocks", "unpack_blocks", "pack_supported", 
            "argreduce_decode", "argreduce_supported", "topk_rows", "gemm_f32", "gemm_h3", "h3_planes", "H3Planes",
            "gemm_h3_planes", "gemm64", "gemm_f64", "cholesky_upper", "tri_inv_upper", "householder_qr",
            "householder_factor", "householder_apply", "householder_block", "vtc64", "gram64",
-           "radix_sort_supported", "sort_rows"]
+           "radix_sort_supported", "sort_rows", "class_moments", "gnb_jll", "GNB_MAX_CLASSES"]
 
 _NUM_CUS = {}
 
@@ -772,6 +772,98 @@ def moments4(x: torch.Tensor, axis: Optional[int] = None):
     d = xd - mean.unsqueeze(axis)
     d2 = d * d
     return n, mean, d2.sum(dim=axis), (d2 * d).sum(dim=axis), (d2 * d2).sum(dim=axis)
+
+
+# --------------------------------------------------------------------------------------------- naive Bayes
+GNB_MAX_CLASSES = 64   # what csrc/gnb.hip serves (4 class tiles of 16)
+
+
+def _gnb_native(X: torch.Tensor, k: int) -> bool:
+    return (X.dim() == 2 and use_native(X) and X.dtype in (torch.float32, torch.float64) and 0 < k <= GNB_MAX_CLASSES
+            and X.shape[0] > 0 and 0 < X.shape[1] < 2 ** 31)
+
+
+def _gnb_rows(X: torch.Tensor) -> torch.Tensor:
+    """X with unit stride along the features (any row stride), as the gnb kernels read it."""
+    return X if X.stride(1) == 1 and (X.shape[0] == 1 or X.stride(0) >= X.shape[1]) else X.contiguous()
+
+
+def class_moments(X: torch.Tensor, idx: torch.Tensor, k: int, weights: Optional[torch.Tensor] = None):
+    """Per-class weighted (count [k], mean [k, f], M2 [k, f]) of the rows of ``X`` [m, f] as float64
+    tensors: row i counts with ``weights[i]`` (1 without weights) for class ``idx[i]`` in [0, k), and
+    ``M2 = sum w (x - mean)^2``. A class without rows gets (0, 0, 0).
+
+    Device float32 / float64 ``X`` with ``k <= 64``: ONE pass over ``X`` (``csrc/gnb.hip``: a weighted
+    one-hot product on the float64 matrix cores, shifted sums per row chunk, Chan merge of the chunks in
+    index order) - no float64 copy, no atomics, bit-identical run to run. Everything else: the two-pass
+    ``index_add_`` expression."""
+    m, f = X.shape
+    if _gnb_native(X, k):
+        L = lib()
+        dev = X.device
+        Xc = _gnb_rows(X)
+        ix = idx.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+        w = None if weights is None else weights.reshape(-1).to(device=dev, dtype=torch.float64).contiguous()
+        if ix.numel() != m or (w is not None and w.numel() != m):
+            raise ValueError("class_moments: idx and weights need one entry per row of X")
+        dt = 0 if X.dtype == torch.float32 else 1
+        nchunks = L.ha_gnb_moments_chunks(m, f, k, dt, num_cus(dev))
+        ws = L.ha_gnb_moments_workspace(nchunks, k, f)
+        part = torch.empty(ws, dtype=torch.float64, device=dev) if ws else None
+        out = torch.empty((3, k, f), dtype=torch.float64, device=dev)
+        check(L.ha_gnb_moments(_ptr(Xc), dt, m, f, Xc.stride(0) if m > 1 else f, _ptr(ix), _ptr(w), k, nchunks,
+                               _ptr(part), _ptr(out), ctypes.c_void_p(stream_ptr(dev))), "ha_gnb_moments")
+        return out[0, :, 0], out[1], out[2]
+    Xd = X.to(torch.float64)
+    ix = idx.reshape(-1).to(device=X.device, dtype=torch.int64)
+    w = torch.ones(m, dtype=torch.float64, device=X.device) if weights is None else \
+        weights.reshape(-1).to(device=X.device, dtype=torch.float64)
+    cnt = torch.zeros(k, dtype=torch.float64, device=X.device).index_add_(0, ix, w)
+    sums = torch.zeros(k, f, dtype=torch.float64, device=X.device).index_add_(0, ix, Xd * w.unsqueeze(1))
+    mu = torch.where(cnt.unsqueeze(1) > 0, sums / cnt.clamp(min=1e-300).unsqueeze(1), torch.zeros_like(sums))
+    m2 = torch.zeros(k, f, dtype=torch.float64, device=X.device).index_add_(0, ix, (Xd - mu[ix]) ** 2 * w.unsqueeze(1))
+    return cnt, mu, m2
+
+
+_GNB_MODES = {"jll": 0, "argmax": 1, "log_proba": 2}
+
+
+def gnb_jll(X: torch.Tensor, theta: torch.Tensor, sigma: torch.Tensor, log_prior: torch.Tensor, out: str = "jll"):
+    """Gaussian naive Bayes joint log likelihood of the rows of ``X`` [m, f] under k classes,
+    ``jll[i, c] = log_prior[c] - 0.5 sum_f log(2 pi sigma[c, f]) - 0.5 sum_f (x[i, f] - theta[c, f])^2 / sigma[c, f]``
+    in ``X``'s precision and in the difference form. ``out``: ``"jll"`` the [m, k] matrix, ``"argmax"`` the
+    int64 [m] class of the largest entry (ties to the lowest class), ``"log_proba"`` jll - logsumexp(jll).
+
+    Device float32 / float64 ``X`` with ``k <= 64``: one pass over ``X`` and no temporary beyond the
+    result (``csrc/gnb.hip``). Everything else: the torch expression."""
+    mode = _GNB_MODES[out]
+    k = theta.shape[0]
+    m, f = X.shape
+    if _gnb_native(X, k):
+        L = lib()
+        dev = X.device
+        Xc = _gnb_rows(X)
+        th, sg = (t.to(device=dev, dtype=X.dtype) for t in (theta, sigma))
+        th = th if th.stride(1) == 1 else th.contiguous()
+        sg = sg if sg.stride(1) == 1 else sg.contiguous()
+        lp = log_prior.reshape(-1).to(device=dev, dtype=X.dtype).contiguous()
+        if th.shape != (k, f) or sg.shape != (k, f) or lp.numel() != k:
+            raise ValueError("gnb_jll: theta and sigma must be [k, f] and log_prior [k]")
+        dt = 0 if X.dtype == torch.float32 else 1
+        work = torch.empty(L.ha_gnb_jll_work(k, f, dt), dtype=X.dtype, device=dev)
+        res = torch.empty(m, dtype=torch.int64, device=dev) if mode == 1 else \
+            torch.empty((m, k), dtype=X.dtype, device=dev)
+        check(L.ha_gnb_jll(_ptr(Xc), dt, m, f, Xc.stride(0) if m > 1 else f, _ptr(th), th.stride(0), _ptr(sg),
+                           sg.stride(0), _ptr(lp), k, mode, _ptr(work), _ptr(res),
+                           ctypes.c_void_p(stream_ptr(dev))), "ha_gnb_jll")
+        return res
+    th, sg, lp = (t.to(device=X.device, dtype=X.dtype) for t in (theta, sigma, log_prior))
+    n_ij = -0.5 * torch.sum(torch.log(2.0 * torch.pi * sg), 1)
+    quad = ((X.unsqueeze(1) - th.unsqueeze(0)) ** 2 / sg.unsqueeze(0)).sum(2)
+    jll = lp.reshape(1, -1) + n_ij.unsqueeze(0) - 0.5 * quad
+    if mode == 1:
+        return torch.argmax(jll, dim=1)
+    return jll - torch.logsumexp(jll, dim=1, keepdim=True) if mode == 2 else jll
 
 
 # --------------------------------------------------------------------------------------------- cdist

@@ -33,7 +33,7 @@ _COLLECTIVES = ["Allreduce", "Iallreduce", "Bcast", "Ibcast", "Allgather", "Allg
                 "Alltoall", "Alltoallv", "Gatherv", "Scatterv", "Exscan", "Scan", "Reduce", "Send", "Recv", "Isend",
                 "Irecv", "exchange", "allgather_tensor", "Barrier", "bcast", "allgather", "allreduce"]
 _KERNELS = ["kmeans_assign", "kmeans_update", "kmeans_assign_f64", "kmeans_update_f64", "kmeans_step_small", "moments",
-            "cdist", "lasso_epoch", "knn_topk", "gemm_f16x3"]
+            "cdist", "lasso_epoch", "knn_topk", "gemm_f16x3", "class_moments", "gnb_jll"]
 
 _state = {"enabled": False, "timing": False, "originals": {}}
 _counters: Dict[str, Dict[str, float]] = defaultdict(lambda: {"calls": 0, "bytes": 0, "ms": 0.0})
