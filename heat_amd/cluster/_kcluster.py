@@ -48,6 +48,7 @@ class _KCluster(ClusteringMixin, BaseEstimator):
         self._certify = True
         self._cert_probe = None
         self._cert_calls = 0
+        self._cert_host = None  # pinned int32 word the re-check count is posted to
 
     CERT_MAX_RECHECK = 0.35
 
@@ -67,7 +68,10 @@ class _KCluster(ClusteringMixin, BaseEstimator):
         labels, _ = ops.kmeans_assign(X, C, want_mind=False, packed=packed, certified=certified)
         self._cert_calls += 1
         if certified and X.shape[0] > 0:
-            host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+            # one pinned word per estimator: the previous count was read (above) before this call
+            host = self._cert_host
+            if host is None:
+                host = self._cert_host = torch.empty(1, dtype=torch.int32, pin_memory=True)
             host.copy_(ops.kernels.kmeans_assign.last_rechecked.reshape(1), non_blocking=True)  # unwrapped by profiling
             ev = torch.cuda.Event()
             ev.record()

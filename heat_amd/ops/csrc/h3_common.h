@@ -19,6 +19,8 @@ __device__ __forceinline__ unsigned h3_bf16_rn(float x) {
   return (b + 0x7FFFu + ((b >> 16) & 1u)) >> 16;
 }
 __device__ __forceinline__ float h3_bf16_f(unsigned b) { return __uint_as_float(b << 16); }
+// fp32 -> bf16 bits, rounded up (x >= 0, finite)
+__device__ __forceinline__ unsigned h3_bf16_up(float x) { return (__float_as_uint(x) + 0xFFFFu) >> 16; }
 
 constexpr int H3_AMB_SHARDS = 16;  // lists of the certified filter's uncertain points
 
@@ -73,8 +75,11 @@ __global__ __launch_bounds__(256) void h3_pack_points(const float* __restrict__ 
 // max |c_i| and |c|^2 -> ur[chunk][0:CB) = u_c = |c|^2 / 2 (+inf for padding rows) and
 // ur[chunk][CB:2CB) = r_c = 2^e (max |c_i| 2^-e in [0.5, 1); 1 for zero / padding rows), plus
 // meta[1] = max_c max_i |c_i| and meta[2] = max_c u_c (float bits, atomicMax on zeroed words: valid
-// for non-negative floats; used by the certified filter's error bound). u and r of one chunk are
-// adjacent so ONE LDS-DMA instruction stages both. h3_pack_centroids: the packed image
+// for non-negative floats; used by the certified top-k's error bound). u and r of one chunk are
+// adjacent so ONE LDS-DMA instruction stages both. The rank-1 fragments also carry the certified
+// filter's per-centroid error coefficients, rounded up to bf16 (see h1_filter): k-slot 3 holds
+// s_c g_c, g_c = 1.08 2^-10 |c|, and k-slot 8 (lane j + 32) s_c 2^-14 u_c; every other kernel's
+// B fragment is zero in those slots. h3_pack_centroids: the packed image
 //   image[chunk][cb][ks][hl][lane][8] (lane = h*32 + j, centroid chunk*CB + cb*32 + j,
 //   features h*F2 + 8 ks .. +8) of c * s_c split into fp16 hi / lo.
 template <int FPAD>
@@ -109,7 +114,7 @@ __global__ __launch_bounds__(256) void h3_cscale(const float* __restrict__ C, in
     if (g8 != 0 || c >= kpad) continue;
     float* urc = ur + (int64_t)(c / CB) * 2 * CB + c % CB;
     // rank-1 A fragment of the -s_c u_c term (see h3_assign_p): lane j of tile c/32 holds its three
-    // bf16 pieces in k-slots 0..2, lane j + 32 (k-slots 8..15) zeros
+    // bf16 pieces in k-slots 0..2, its filter coefficients in k-slot 3 and in k-slot 8 (lane j + 32)
     unsigned* vc = vimg + ((int64_t)(c / 32) * 64 + c % 32) * 2;
     vc[64] = 0u;
     vc[65] = 0u;
@@ -131,7 +136,8 @@ __global__ __launch_bounds__(256) void h3_cscale(const float* __restrict__ C, in
       const unsigned mid = h3_bf16_rn(r1);
       const unsigned lo = h3_bf16_rn(r1 - h3_bf16_f(mid));
       vc[0] = hi | (mid << 16);
-      vc[1] = lo;
+      vc[1] = lo | (h3_bf16_up(ldexpf(1.08f * 0x1p-10f * sqrtf(sq), -e)) << 16);
+      vc[64] = h3_bf16_up(ldexpf(0x1p-15f * sq, -e));
     }
     if (mx > 0.f && mx < __builtin_huge_valf()) bmx = fmaxf(bmx, mx);
     if (sq > 0.f && sq < __builtin_huge_valf()) bu = fmaxf(bu, 0.5f * sq);

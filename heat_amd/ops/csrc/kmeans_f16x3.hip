@@ -234,19 +234,45 @@ __global__ __launch_bounds__(256, MINB) void h3_assign_p(const _Float16* __restr
 }
 
 // Certified one-term filter ("h1"). Scores use hi_c . hi_x only (ONE MFMA per k-step instead of
-// three), the kernel tracks each point's best AND runner-up score, and a point is assigned here
-// only if its best score beats the runner-up by more than twice a rigorous bound E on the
-// hi-only error; every other point is appended to `amb_rows` and re-run through the 3-term kernel
-// (IND mode of h3_assign_p). In the scaled space (|x_s|_inf, |c_s|_inf < 1), with a, b the fp16
-// rounding errors of x_s, c_s (|a_i| <= 2^-11 |x_s,i| or 2^-25 in fp16's subnormal range):
-//   |x_s.c_s - hi_x.hi_c| <= sum |x_i b_i| + |a_i c_i| + |a_i b_i| <= 2^-10 (1 + 2^-11) |x_s| |c_s| + f 2^-24
-// fp16 x fp16 products are exact in fp32; the fp32 accumulation, the fp32 |c|^2 and the epilogue
-// FMA add <= (f + 2) 2^-24 (|x_s||c_s| + s_x u_max); f <= 128 gives
-//   E = 1.01 * 2^-10 |x_s| c_max + 2^-16 (|x_s| c_max + s_x u_max) + 2^-16,
-// with |x_s| bounded from the hi plane (|x_s| <= |hi_x| (1 + 2^-10)) and c_max = max_c |c_s|.
-// The runner-up is exact without a per-value second-best update: per lane it is the larger of the
-// second-largest TILE maximum (one med3 per tile) and the second-largest value of the best tile
-// (whose 16 values are kept anyway to recover the index).
+// three). Every centroid c gets its OWN rigorous bound E_c(x) on the error of its one-term score;
+// a point is assigned here only if the lower bound of its best score exceeds the upper bound of
+// every other centroid's score. Every other point is appended to `amb_rows` and re-run through
+// the 3-term kernel (IND mode of h3_assign_p). A bound shared by all centroids (2^-10 |x_s| times
+// the LARGEST centroid norm) certified almost nothing on the benchmark's Lloyd run: from the third
+// step on one centroid has norm 173 beside a median norm of 3.2, and 98.7 % of the points were
+// re-run (profiles/kmeans_certified_r10.md).
+//
+// The bound. S_c = s_x (x.c - |c|^2/2) is the exact score, S~_c the computed one. In the scaled
+// space (|x_s|_inf, |c_s|_inf < 1), with a, b the fp16 rounding errors of x_s, c_s (|a_i| <=
+// 2^-11 |x_s,i|, or 2^-25 in fp16's subnormal range), times r_c = 1 / s_c (exact):
+//  (1) hi-only product: sum |x_i b_i| + |a_i c_i| + |a_i b_i| <= 2^-10 (1 + 2^-11) |x_s||c|, plus
+//      f 2^-24 r_c from subnormal components; r_c <= 2 |c|, f <= 128 and |x_s| >= 1/2 (x = 0 has
+//      no error at all) turn that into <= 2^-15 |x_s||c|;
+//  (2) fp32 accumulation of the f products, the three u pieces and the two bound terms below
+//      (fp16 x fp16 and bf16 x bf16 products are exact): (f + 5) 2^-24 <= 1.04 2^-17 relative to
+//      the sum of magnitudes <= (1 + 2^-9) (|x_s||c| + s_x u_c);
+//  (3) u_c: the fp32 |c|^2 (<= (f + 2) 2^-24 <= 1.02 2^-17 relative) and its 3-piece bf16 split
+//      (2^-24).
+// Sum: (2^-10 (1 + 2^-11) + 2^-15 + 1.05 2^-17) |x_s||c| + (1.05 2^-17 + 1.02 2^-17 + 2^-24) s_x u_c
+//      <= 1.04 2^-10 |x_s||c| + 1.04 2^-16 s_x u_c.
+// Term (2) assumes that the MFMA accumulates in round-to-nearest fp32 (error <= 2^-24 per add); a
+// truncating accumulate (2^-23 per add) would double it, to 1.048 2^-10 |x_s||c| + 1.56 2^-16 s_x u_c.
+// h3_cscale rounds g_c = 1.08 2^-10 |c| and 2^-14 u_c (scaled by s_c) UP to bf16, the kernel rounds
+// xn >= |x_s| up to bf16 (from the hi plane: |x_s| <= |hi_x| (1 + 2^-10), and 2^-9 for the fp32
+// sum and root), and   E_c(x) = xn g_c + s_x 2^-14 u_c   exceeds the sum above by > 3.8 % of it (> 3 %
+// even under truncation), which covers the fp32 roundings of g_c, of xn and of the final L_b below
+// (a few 2^-24 relative each).
+// Both terms ride in two spare k-slots of the rank-1 bf16 MFMA that adds -s_x u_c (as in
+// h3_assign_p), so an accumulator times r_c IS the upper score U_c = S~_c + E_c >= S_c, and the
+// epilogue is one multiply per pair plus the maxima. With b = argmax U the lower bound is
+// L_b = U_b - 2 E_b <= S_b (E_b from b's coefficients, one gather per point); L_b > U_c for every
+// c != b proves b the exact argmax.
+// The runner-up max_{c != b} U_c is exact without a per-value second-best update. Per lane the
+// centroids are partitioned twice, into tiles and into the 16 accumulator slots: the kernel keeps
+// the best and second-best TILE maximum (one med3 per tile) and the maximum of every SLOT over all
+// tiles (one max per pair). Two centroids of a lane differ in tile or in slot, so the runner-up is
+// the larger of the second-best tile maximum and the second-best slot maximum, and the best
+// slot is the index within the best tile: no value is carried to recover it.
 template <int FPAD, int NPB_ = 2, int MINB = 2>
 __global__ __launch_bounds__(256, MINB) void h1_filter(const _Float16* __restrict__ planes, const float* __restrict__ sxv,
                                                  int64_t n, const _Float16* __restrict__ image,
@@ -264,7 +290,8 @@ __global__ __launch_bounds__(256, MINB) void h1_filter(const _Float16* __restric
   const int64_t pbase = (int64_t)blockIdx.x * K::PTS_PER_WG + (int64_t)wave * (NPB * 32);
 
   halfx8 bhi[NPB][KS];
-  float nsx[NPB], hsq[NPB];
+  bf16x8 bsx[NPB];
+  float sx[NPB], xn[NPB];
 #pragma unroll
   for (int pb = 0; pb < NPB; ++pb) {
     int64_t row = pbase + pb * 32 + j;
@@ -277,12 +304,19 @@ __global__ __launch_bounds__(256, MINB) void h1_filter(const _Float16* __restric
 #pragma unroll
       for (int i = 0; i < 8; ++i) q = fmaf((float)bhi[pb][ks][i], (float)bhi[pb][ks][i], q);
     }
-    nsx[pb] = -sxv[row];
-    hsq[pb] = q;
+    sx[pb] = sxv[row];
+    // xn >= |x_s|, rounded up to bf16 (exactly the value the MFMA multiplies g_c with)
+    const unsigned xb = h3_bf16_up(sqrtf(q + __shfl_xor(q, 32, 64)) * (1.f + 0x1p-10f + 0x1p-9f));
+    xn[pb] = h3_bf16_f(xb);
+    // B fragment of the rank-1 term: s_x (a power of two: exact in bf16) against the three u
+    // pieces (k-slots 0..2) and against 2^-14 u_c (k-slot 8), xn against g_c (k-slot 3)
+    const unsigned sb = __float_as_uint(sx[pb]) >> 16;
+    const u32x4 bw = {h ? sb : (sb | (sb << 16)), h ? 0u : (sb | (xb << 16)), 0u, 0u};
+    bsx[pb] = __builtin_bit_cast(bf16x8, bw);
   }
   float best[NPB], sec[NPB];
   int btile[NPB];
-  float sv[NPB][16];
+  float sv[NPB][16];  // maximum of every accumulator slot over all tiles
 #pragma unroll
   for (int pb = 0; pb < NPB; ++pb) {
     best[pb] = NINF;
@@ -294,40 +328,31 @@ __global__ __launch_bounds__(256, MINB) void h1_filter(const _Float16* __restric
 
   // only the hi half of every (cb, ks) fragment pair is staged: piece 2q of the chunk -> LDS q
   constexpr int PIECES = CHUNK_H * 2 / 1024 / 2;
-  constexpr int BUF = CHUNK_H + CB * 8;  // two buffers, as in h3_assign_p
+  constexpr int VPIECES = CB * 16 / 1024;  // rank-1 fragments: 512 B per 32-centroid tile
+  constexpr int BUF = CHUNK_H + CB * 8 + CB * 16;  // two buffers, as in h3_assign_p
+  const unsigned* vimg = reinterpret_cast<const unsigned*>(meta + 4);
   floatx16 acc[2][NPB];
   const float* pu = nullptr;  // LDS u/r of the tile whose epilogue is pending
   int ptile = -1;
   auto epilogue = [&](const floatx16 (&ac)[NPB], const float* pu_, int tile) {
-    // u and r of the tile straight from LDS (the chunk buffer is still live: see the loop)
-    floatx4 cn[4], cr[4];
+    // r of the tile straight from LDS (the chunk buffer is still live: see the loop); the
+    // accumulator holds s_c U_c (rank-1 MFMA), so the upper score is ONE multiply
+    floatx4 cr[4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      cn[g] = *reinterpret_cast<const floatx4*>(pu_ + 8 * g + 4 * h);
-      cr[g] = *reinterpret_cast<const floatx4*>(pu_ + CB + 8 * g + 4 * h);
-    }
+    for (int g = 0; g < 4; ++g) cr[g] = *reinterpret_cast<const floatx4*>(pu_ + CB + 8 * g + 4 * h);
 #pragma unroll
     for (int pb = 0; pb < NPB; ++pb) {
-      const floatx2 sx2 = {nsx[pb], nsx[pb]};
       float w[16];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const floatx2 c2 = {cn[q >> 1][(2 * q) & 3], cn[q >> 1][(2 * q + 1) & 3]};
-        const floatx2 rc2 = {cr[q >> 1][(2 * q) & 3], cr[q >> 1][(2 * q + 1) & 3]};
-        const floatx2 a2 = {ac[pb][2 * q], ac[pb][2 * q + 1]};
-        const floatx2 r2 = h3_score2(a2, rc2, c2, sx2);
-        w[2 * q] = r2[0];
-        w[2 * q + 1] = r2[1];
-      }
+      for (int q = 0; q < 16; ++q) w[q] = ac[pb][q] * cr[q >> 2][q & 3];
       float m = w[0];
 #pragma unroll
       for (int r = 1; r < 16; ++r) m = fmaxf(m, w[r]);
       sec[pb] = __builtin_amdgcn_fmed3f(best[pb], sec[pb], m);
-      const bool imp = m > best[pb];
-      best[pb] = imp ? m : best[pb];
-      btile[pb] = imp ? tile : btile[pb];
+      btile[pb] = m > best[pb] ? tile : btile[pb];
+      best[pb] = fmaxf(best[pb], m);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) sv[pb][r] = imp ? w[r] : sv[pb][r];
+      for (int r = 0; r < 16; ++r) sv[pb][r] = fmaxf(sv[pb][r], w[r]);
     }
   };
   for (int ch = 0; ch < nchunks; ++ch) {
@@ -341,11 +366,17 @@ __global__ __launch_bounds__(256, MINB) void h1_filter(const _Float16* __restric
       if (wave == 0 && lane < CB / 2)  // u and r of the chunk (adjacent)
         __builtin_amdgcn_global_load_lds(reinterpret_cast<const char*>(u + ch * 2 * CB) + lane * 16,
                                          (__attribute__((address_space(3))) void*)(dst + CHUNK_H), 16, 0, 0);
+#pragma unroll
+      for (int pc = wave; pc < VPIECES; pc += 4)  // rank-1 fragments of the chunk's tiles
+        __builtin_amdgcn_global_load_lds(reinterpret_cast<const char*>(vimg) + (int64_t)ch * CB * 16 + pc * 1024 + lane * 16,
+                                         (__attribute__((address_space(3))) void*)(dst + CHUNK_H + CB * 8 + pc * 1024),
+                                         16, 0, 0);
       __builtin_amdgcn_s_waitcnt(0);
       __syncthreads();
     }
     const _Float16* img = reinterpret_cast<const _Float16*>(smem + (ch & 1) * BUF);
     const float* ub = reinterpret_cast<const float*>(smem + (ch & 1) * BUF + CHUNK_H);
+    const unsigned* vb = reinterpret_cast<const unsigned*>(smem + (ch & 1) * BUF + CHUNK_H + CB * 8);
 #pragma unroll
     for (int cb = 0; cb < CB / 32; ++cb) {
       const int cur = cb & 1;
@@ -358,21 +389,30 @@ __global__ __launch_bounds__(256, MINB) void h1_filter(const _Float16* __restric
         for (int pb = 0; pb < NPB; ++pb)
           acc[cur][pb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, bhi[pb][ks], acc[cur][pb], 0, 0, 0);
       }
+      {
+        // + s_x (-s_c u_c) + s_c E_c as one bf16 MFMA (exact products, fp32 accumulation)
+        const uint2 vv = *reinterpret_cast<const uint2*>(vb + (cb * 64 + lane) * 2);
+        const u32x4 aw = {vv.x, vv.y, 0u, 0u};
+        const bf16x8 av = __builtin_bit_cast(bf16x8, aw);
+#pragma unroll
+        for (int pb = 0; pb < NPB; ++pb)
+          acc[cur][pb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bsx[pb], acc[cur][pb], 0, 0, 0);
+      }
       if (ptile >= 0) epilogue(acc[cur ^ 1], pu, ptile);
       ptile = ch * (CB / 32) + cb;
       pu = ub + cb * 32;
+      // ~44 VALU per point block and tile (16 multiplies, 16 slot maxima, the 16-way maximum, the
+      // tile bookkeeping) against (KS + 1) MFMAs
 #pragma unroll
-      for (int i = 0; i < KS * NPB; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
-        __builtin_amdgcn_sched_group_barrier(0x002, 12, 0);  // then up to 12 VALU
+      for (int i = 0; i < (KS + 1) * NPB; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                     // 1 MFMA
+        __builtin_amdgcn_sched_group_barrier(0x002, (44 + KS) / (KS + 1), 0);  // then its share of the VALU
       }
     }
     __syncthreads();
   }
   if (ptile >= 0) epilogue(acc[((CB / 32) - 1) & 1], pu, ptile);
 
-  const float umax = meta[2];
-  const float cmax = sqrtf(2.f * umax);  // max_c |c|_2 (unscaled: scores are s_x (x.c - |c|^2/2))
   // uncertain points are appended to one of H3_AMB_SHARDS lists (shard = blockIdx % shards, rows
   // of shard s at amb_rows[s * cap ..), count amb_count[s]) with ONE atomic per workgroup: a
   // wave-level atomic on a single counter serialised ~350K same-address adds on diffuse data
@@ -382,6 +422,7 @@ __global__ __launch_bounds__(256, MINB) void h1_filter(const _Float16* __restric
   int64_t arow[NPB];
 #pragma unroll
   for (int pb = 0; pb < NPB; ++pb) {
+    // t1 = best[pb] sits in the best tile's best slot; t2 = the second-best slot maximum
     float t1 = NINF, t2 = NINF;
     int bi = 15;
 #pragma unroll
@@ -396,18 +437,19 @@ __global__ __launch_bounds__(256, MINB) void h1_filter(const _Float16* __restric
     const float ob = __shfl_xor(best[pb], 32, 64);
     const float os = __shfl_xor(s2, 32, 64);
     const int oi = __shfl_xor(bidx, 32, 64);
-    const float xn = sqrtf(hsq[pb] + __shfl_xor(hsq[pb], 32, 64)) * (1.f + 0x1p-10f);
     s2 = fmaxf(fminf(best[pb], ob), fmaxf(s2, os));
     float b = best[pb];
     if (ob > b || (ob == b && oi < bidx)) {
       b = ob;
       bidx = oi;
     }
-    const float xc = xn * cmax;
-    const float E = 1.01f * 0x1p-10f * xc + 0x1p-16f * (xc - nsx[pb] * umax) + 0x1p-15f * cmax;
+    // E_b from the winner's own coefficients (the bf16 values the MFMA used, times r_b)
+    const float rb = u[(bidx / CB) * 2 * CB + CB + bidx % CB];
+    const unsigned* vcb = vimg + ((bidx >> 5) * 64 + (bidx & 31)) * 2;
+    const float E = rb * (xn[pb] * h3_bf16_f(vcb[1] >> 16) + sx[pb] * h3_bf16_f(vcb[64] & 0xFFFFu));
     const int64_t row = pbase + pb * 32 + j;
     const bool live = h == 0 && row < n;
-    const bool amb = live && !(b - s2 > 2.f * E);
+    const bool amb = live && !(b - 2.f * E > s2);
     if (live) labels[row] = bidx;
     am[pb] = __ballot(amb);
     arow[pb] = row;
@@ -668,7 +710,7 @@ HA_EXPORT int ha_h3_assign(const void* planes, const float* sx, int64_t n, int f
   case FP: {                                                                                                \
     constexpr int NPB = FP >= 128 ? 1 : 2, MINB = 2;  /* 2 chunk buffers (~66 KB) per WG: 2 WGs/CU */                                        \
     using KC = H3Cfg<FP, NPB>;                                                                              \
-    /* no memset of meta[1..2]: only h1_filter reads them (bench A/B: -12 us per step) */                  \
+    /* no memset of meta[1..2]: no assignment kernel reads them (bench A/B: -12 us per step) */            \
     hipLaunchKernelGGL(h3_cscale<FP>, dim3(h3_cscale_grid(kpad, FP / 8)), dim3(256), 0, s, C, k, f, ldc, kpad, u, meta, (unsigned*)(meta + 4));         \
     hipLaunchKernelGGL(h3_pack_centroids<FP>, dim3((unsigned)(((int64_t)kpad * (FP / 8) + 255) / 256)),  \
                        dim3(256), 0, s, C, k, f, ldc, kpad, image, u);                               \
@@ -735,11 +777,11 @@ HA_EXPORT int ha_h3_assign_certified(const void* planes, const float* sx, int64_
     constexpr int NPB1 = FP >= 128 ? 1 : 2, MINB1 = 2;                                                      \
     using KC = H3Cfg<FP, NPB>;                                                                              \
     using K1 = H3Cfg<FP, NPB1>;                                                                             \
-    hipMemsetAsync(meta, 0, 4 * sizeof(float), s);                                                          \
+    /* no memset of meta[1..2]: h1_filter's bound is per centroid (the rank-1 fragments) */                \
     hipLaunchKernelGGL(h3_cscale<FP>, dim3(h3_cscale_grid(kpad, FP / 8)), dim3(256), 0, s, C, k, f, ldc, kpad, u, meta, (unsigned*)(meta + 4));         \
     hipLaunchKernelGGL(h3_pack_centroids<FP>, dim3((unsigned)(((int64_t)kpad * (FP / 8) + 255) / 256)),  \
                        dim3(256), 0, s, C, k, f, ldc, kpad, image, u);                               \
-    const size_t lds1 = 2 * ((size_t)K1::CHUNK_H + K1::CB * 8);                                                   \
+    const size_t lds1 = 2 * ((size_t)K1::CHUNK_H + K1::CB * 8 + K1::CB * 16);                               \
     const unsigned blocks1 = (unsigned)((n + K1::PTS_PER_WG - 1) / K1::PTS_PER_WG);                        \
     hipFuncSetAttribute(reinterpret_cast<const void*>(h1_filter<FP, NPB1, MINB1>),                          \
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);                             \
