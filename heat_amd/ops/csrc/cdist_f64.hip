@@ -8,20 +8,15 @@
 //     0, then sqrt / nothing / exp(-scale d2), then the store.
 //   * 128 x 128 outputs per 4-wave workgroup, each wave 64 x 64 = 4 x 4 accumulator blocks (128
 //     registers per lane), two workgroups per CU so one tile's epilogue overlaps the other's MFMAs;
-//   * both operands are k-contiguous ([rows][f]) and use ONE LDS image, gemm_f64.hip's
-//     [k/2][row][2]: a 16-byte LDS-DMA lane is two consecutive features of one row, and a lane's
-//     ds_read_b128 of its row's pair kk feeds both MFMA k-steps of the stage (k-slot kk of step s
-//     holds feature 2 kk + s on both sides); 16 lanes read 256 contiguous bytes;
-//   * ring of 4 stages of 8 features (16 KB each), 3 in flight behind a counted vmcnt and one raw
-//     s_barrier per stage. f here is 3 to a few hundred, so the loop is written for short trip
-//     counts: fewer stages than the ring (down to f = 1), f no multiple of 8 and odd f all run the
-//     same guarded steps; the tail stage is clamped at the load and zeroed in LDS after it lands;
-//   * row norms come from cdist_f64_norms (16 lanes per row, lane l sums features l, l + 16, ... in
-//     order, then a fixed xor tree: bit-identical for a row wherever it sits), m + n doubles of
-//     workspace read per tile in the epilogue; X == Y computes them once. The pre-pass reads
-//     (m + n) f values against m n written: f (1 / m + 1 / n) of the store traffic, below 1 % for
-//     the 40000 x 40000 shapes up to f = 200 and no longer negligible once min(m, n) < ~10 f
-//     (a handful of medoids against many features);
+//   * both operands are k-contiguous ([rows][f]) and come through the 4-slot staging ring that
+//     f64_ring.h describes (image, pipeline, tail). f here is 3 to a few
+//     hundred, so the loop is written for short trip counts: fewer stages than the ring (down to
+//     f = 1), f no multiple of 8 and odd f all run the same guarded steps;
+//   * row norms come from f64_row_norms (f64_ring.h: bit-identical for a row wherever it sits),
+//     m + n doubles of workspace read per tile in the epilogue; X == Y computes them once. The
+//     pre-pass reads (m + n) f values against m n written: f (1 / m + 1 / n) of the store traffic,
+//     below 1 % for the 40000 x 40000 shapes up to f = 200 and no longer negligible once
+//     min(m, n) < ~10 f (a handful of medoids against many features);
 //   * stores are non-temporal. Which operand feeds the MFMA's A side decides what a lane owns (the
 //     f64 16x16x4 C/D map is column = lane & 15, row = (lane >> 4) + 4 g). X is on A: a lane owns
 //     one column of 4 rows, 8-byte stores, 16 lanes = one 128-byte run, any alignment of C.
@@ -34,9 +29,7 @@
 //   * out-of-range rows / columns are clamped at the load and masked at the store;
 //   * 1-D grid in an XCD-aware grouped order: each XCD gets a contiguous run of tiles, in which 8
 //     X tiles at a time sweep all Y tiles (8 consecutive workgroups share one Y tile).
-//   Requirements (made so by the Python wrapper, never by a copy in here): 16-byte aligned X, Y
-//   with even leading dimensions; for odd f the 16-byte load of the last pair also takes the 8
-//   bytes behind feature f - 1, which must be readable (they are zeroed in LDS).
+//   Requirements (made so by the Python wrapper, never by a copy in here): the ring's, on X and Y.
 //
 // (b) cdist_f64_vx, modes 3-6: sum |x - y| or sum (x - y)^2 on the fp64 VALU, the only form without
 //     cancellation for near-identical rows.
@@ -62,7 +55,7 @@
 //   cdist_f64_mm<OP>           216      0     76     65536        0       2
 //   cdist_f64_vx<OP, false>    242      0  47-56     66560        0       2
 //   cdist_f64_vx<OP, true>     244      0  30-56     66560        0       2
-//   cdist_f64_norms             12      0     20         0        0       8
+//   f64_row_norms               12      0     20         0        0       8
 // 2 waves per SIMD = two workgroups per CU for both tile kernels; the 8 x 8 fp64 VALU tile does not
 // spill, so the 8 x 4 fallback was not needed.
 //
@@ -86,14 +79,11 @@
 // measured. The VALU kernel at f = 128 issues 2 f fp64 operations per pair at 25 T lane-operations
 // per second (65 % of the VALU's fp64 issue rate); from where on in f it is compute-bound was not
 // measured beyond these two points.
-#include "common.h"
+#include "f64_ring.h"
 
 #include <cmath>
 
 namespace {
-
-typedef double doublex2 __attribute__((ext_vector_type(2)));
-typedef double doublex4 __attribute__((ext_vector_type(4)));
 
 // OP of both kernels' epilogue: what becomes of the summed value v (d2, or d1 for manhattan)
 enum { OP_L1 = 0, OP_EUCLID = 1, OP_SQ = 2, OP_GAUSS = 3 };
@@ -109,76 +99,10 @@ __device__ __forceinline__ void cf_store2(double* p, double a, double b) {
   __builtin_nontemporal_store((doublex2){a, b}, reinterpret_cast<doublex2*>(p));
 }
 
-// ------------------------------------------------------------------------------------- row norms
-// out[i] = |row i|^2 for the rows of X (i < m) then of Y (i - m < n; n = 0: X only)
-__global__ __launch_bounds__(256) void cdist_f64_norms(const double* __restrict__ X, int64_t m, int64_t ldx,
-                                                       const double* __restrict__ Y, int64_t n, int64_t ldy,
-                                                       int64_t f, double* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-  const int l = threadIdx.x & 15;
-  if (i >= m + n) return;  // whole 16-lane groups leave together
-  const double* row = i < m ? X + i * ldx : Y + (i - m) * ldy;
-  double s = 0.0;
-  for (int64_t k = l; k < f; k += 16) s = fma(row[k], row[k], s);
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
-  if (l == 0) out[i] = s;
-}
-
 // --------------------------------------------------------------------- (a) expansion on the MFMA
-constexpr int CT = 128;            // tile rows / columns
-constexpr int CK = 8;              // features per stage
-constexpr int COP = CT * CK * 8;   // bytes per operand per stage
-constexpr int CSTG = 2 * COP;      // bytes per stage
+constexpr int CT = F64_T;          // tile rows / columns
 constexpr int CNBUF = 4;           // ring slots
 constexpr int CAHEAD = CNBUF - 1;  // stages in flight
-constexpr int CDPS = 4;            // DMA instructions per wave per stage (2 per operand)
-
-// 32-bit: the host caps the grid at 2^31 - 1 tiles
-__device__ __forceinline__ unsigned cf_xcd_remap(unsigned orig, unsigned nwg) {
-  const unsigned q = nwg / 8, r = nwg % 8, xcd = orig % 8, loc = orig / 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-}
-
-// LDS-DMA of 16 bytes per lane to LDS byte address lds + 16 lane (wave-uniform lds); M0 saved /
-// restored around it (the compiler treats M0 as reserved and would not see a clobber)
-__device__ __forceinline__ void cf_dma16(const void* g, unsigned lds) {
-  unsigned saved;
-  const unsigned base = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(saved)
-               : "v"(g), "s"(base)
-               : "memory");
-}
-
-// at most N of this wave's vector-memory ops outstanding, LDS ops retired, then the barrier
-template <int N>
-__device__ __forceinline__ void cf_wait_barrier() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// One operand's staging for this lane: piece q of a stage = feature pair q / 2, tile rows
-// 64 (q % 2) + lane, landing at byte q KB of the operand's image. Out-of-range rows are clamped.
-struct CfSrc {
-  const double* p0;  // tile row lane
-  const double* p1;  // tile row 64 + lane
-  __device__ __forceinline__ void init(const double* P, int64_t ld, int64_t rows, int64_t r0, int lane) {
-    const int64_t a = r0 + lane, b = r0 + 64 + lane;
-    p0 = P + (a < rows ? a : rows - 1) * ld;
-    p1 = P + (b < rows ? b : rows - 1) * ld;
-  }
-  __device__ __forceinline__ const double* src(int64_t k0, int q) const {
-    return ((q & 1) ? p1 : p0) + k0 + 2 * (q >> 1);
-  }
-  // the tail stage: the pair clamped into the row (entries at k >= f are zeroed after they land)
-  __device__ __forceinline__ const double* src_clamped(int64_t k0, int q, int64_t f) const {
-    const int64_t k = k0 + 2 * (q >> 1), last = (f - 1) & ~(int64_t)1;
-    return ((q & 1) ? p1 : p0) + (k < last ? k : last);
-  }
-};
 
 // Fragments of one stage for a wave: p[b][s], q[b][s] = block b's operand for MFMA k-step s.
 struct CfFrag {
@@ -192,46 +116,46 @@ __global__ __launch_bounds__(256, 2) void cdist_f64_mm(const double* __restrict_
                                                        int64_t ldx, int64_t ldy, const double* __restrict__ xn,
                                                        const double* __restrict__ yn, double* __restrict__ C,
                                                        int64_t ldc, double scale) {
-  static_assert(CNBUF * CSTG <= 80 * 1024, "two workgroups per CU");
-  __shared__ __attribute__((aligned(16))) unsigned char smem[CNBUF * CSTG];
+  static_assert(CNBUF * F64_STG <= 80 * 1024, "two workgroups per CU");
+  __shared__ __attribute__((aligned(16))) unsigned char smem[CNBUF * F64_STG];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int kk = lane >> 4, r = lane & 15;
   const unsigned ty = (unsigned)((n + CT - 1) / CT), tx = (unsigned)((m + CT - 1) / CT);
-  const unsigned bid = cf_xcd_remap(blockIdx.x, tx * ty);
+  const unsigned bid = ha_xcd_remap(blockIdx.x, tx * ty);
   constexpr unsigned GM = 8;
   const unsigned grp = bid / (GM * ty), gfirst = grp * GM;
   const unsigned gsz = tx - gfirst < GM ? tx - gfirst : GM;
   const int64_t x0 = (int64_t)(gfirst + (bid % (GM * ty)) % gsz) * CT, y0 = (int64_t)((bid % (GM * ty)) / gsz) * CT;
 
-  CfSrc sp, sq;
+  F64Src<> sp, sq;
   sp.init(X, ldx, m, x0, lane);
   sq.init(Y, ldy, n, y0, lane);
   const unsigned sbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
 
   auto stage = [&](int64_t t, bool full) {
-    const unsigned dst = sbase + (unsigned)((t % CNBUF) * CSTG);
-    const int64_t k0 = t * CK;
+    const unsigned dst = sbase + (unsigned)((t % CNBUF) * F64_STG);
+    const int64_t k0 = t * F64_K;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = 2 * wave + i;
-      cf_dma16(full ? sp.src(k0, q) : sp.src_clamped(k0, q, f), dst + q * 1024);
+      ha_dma16(full ? sp.src(k0, q) : sp.src_clamped(k0, q, f), dst + q * 1024);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = 2 * wave + i;
-      cf_dma16(full ? sq.src(k0, q) : sq.src_clamped(k0, q, f), dst + COP + q * 1024);
+      ha_dma16(full ? sq.src(k0, q) : sq.src_clamped(k0, q, f), dst + F64_OP + q * 1024);
     }
   };
   // this wave's own pieces of the tail stage: the values at k >= f become zero
   auto zero_tail = [&](int64_t t) {
-    unsigned char* dst = smem + (t % CNBUF) * CSTG;
-    const int64_t ka = t * CK + 2 * wave;  // both of this wave's pieces hold the pair ka, ka + 1
+    unsigned char* dst = smem + (t % CNBUF) * F64_STG;
+    const int64_t ka = t * F64_K + 2 * wave;  // both of this wave's pieces hold the pair ka, ka + 1
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = 2 * wave + i;
       double* pa = reinterpret_cast<double*>(dst + q * 1024 + lane * 16);
-      double* pb = reinterpret_cast<double*>(dst + COP + q * 1024 + lane * 16);
+      double* pb = reinterpret_cast<double*>(dst + F64_OP + q * 1024 + lane * 16);
       if (ka >= f) pa[0] = pb[0] = 0.0;
       if (ka + 1 >= f) pa[1] = pb[1] = 0.0;
     }
@@ -247,9 +171,9 @@ __global__ __launch_bounds__(256, 2) void cdist_f64_mm(const double* __restrict_
     }
   };
   auto load = [&](CfFrag& F, int64_t t) {
-    const unsigned char* base = smem + (t % CNBUF) * CSTG;
+    const unsigned char* base = smem + (t % CNBUF) * F64_STG;
     opnd(base, wm * 64, F.p);
-    opnd(base + COP, wn * 64, F.q);
+    opnd(base + F64_OP, wn * 64, F.q);
   };
 
   doublex4 acc[4][4];
@@ -269,18 +193,18 @@ __global__ __launch_bounds__(256, 2) void cdist_f64_mm(const double* __restrict_
           acc[bm][bn] = __builtin_amdgcn_mfma_f64_16x16x4f64(F.p[bm][s], F.q[bn][s], acc[bm][bn], 0, 0, 0);
   };
 
-  const int64_t nk = (f + CK - 1) / CK;
-  const bool tail = (f % CK) != 0;
+  const int64_t nk = (f + F64_K - 1) / F64_K;
+  const bool tail = (f % F64_K) != 0;
   // stage t landed (this wave's DMA) and visible to every wave; later stages may be in flight
   auto ready = [&](int64_t t) {
     const int64_t later = nk - 1 - t < CAHEAD - 1 ? nk - 1 - t : CAHEAD - 1;  // stages issued after t
     if (tail && t == nk - 1) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      ha_vm_wait<0>();
       zero_tail(t);
     }
-    if (later >= 2) cf_wait_barrier<2 * CDPS>();
-    else if (later == 1) cf_wait_barrier<CDPS>();
-    else cf_wait_barrier<0>();
+    if (later >= 2) ha_wait_barrier<2 * F64_DPS>();
+    else if (later == 1) ha_wait_barrier<F64_DPS>();
+    else ha_wait_barrier<0>();
   };
   // steady state (f >= 40): stage t + AHEAD issued whole, the first half of the MFMAs around it,
   // the counted wait for stage t + 1 + barrier, stage t + 1's fragment reads between the second
@@ -289,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void cdist_f64_mm(const double* __restrict_
     stage(t + CAHEAD, true);
     mma_half(Fc, 0);
     __builtin_amdgcn_sched_barrier(0);
-    cf_wait_barrier<(CAHEAD - 1) * CDPS>();
+    ha_wait_barrier<(CAHEAD - 1) * F64_DPS>();
     load(Fn, t + 1);
     mma_half(Fc, 1);
     __builtin_amdgcn_sched_barrier(0);
@@ -560,7 +484,7 @@ HA_EXPORT int ha_cdist_f64(const double* X, int64_t m, const double* Y, int64_t 
   if (tiles > 0x7fffffffLL) return HA_UNSUPPORTED;
   const bool same = X == Y && m == n && ldx == ldy;  // one set of norms
   const int64_t nrows = same ? m : m + n;
-  hipLaunchKernelGGL(cdist_f64_norms, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, s, X, m, ldx, Y,
+  hipLaunchKernelGGL(f64_row_norms, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, s, X, m, ldx, Y,
                      same ? (int64_t)0 : n, ldy, f, ws);
   if (ha_launch_status() != HA_OK) return HA_LAUNCH;
   const double* yn = same ? ws : ws + m;

@@ -25,6 +25,53 @@ __device__ __forceinline__ double ha_wave_sum_d(double v) {
   return v;
 }
 
+// Tile order for a 1-D grid on the 8 XCDs (workgroup i runs on XCD i % 8): each XCD gets a
+// contiguous run of tiles. 32-bit: the hosts cap such grids at 2^31 - 1 tiles (64-bit divisions
+// are long SALU sequences).
+__device__ __forceinline__ unsigned ha_xcd_remap(unsigned orig, unsigned nwg) {
+  const unsigned q = nwg / 8, r = nwg % 8, xcd = orig % 8, loc = orig / 8;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+}
+
+// LDS-DMA of 16 bytes per lane (global_load_lds_dwordx4; LDS address = lds + 16 lane) issued
+// through inline asm: for the builtin the compiler's wait-count pass cannot tell which LDS bytes
+// the transfer writes and puts s_waitcnt vmcnt(0) before the next LDS read - i.e. it waits for
+// the prefetched stages too. The asm form is invisible to that pass (its own vmcnt waits only
+// become more conservative); the kernels wait for their transfers with the counted
+// ha_wait_barrier<N>() / ha_vm_wait<N>().
+// M0 (the LDS address of the transfer) is saved and restored around it: the compiler treats M0 as
+// reserved and would not see a clobber.
+// The LDS address is wave-uniform; readfirstlane pins it to an SGPR (inside a lane-divergent
+// branch the compiler may otherwise hand the "s" operand a VGPR).
+__device__ __forceinline__ void ha_dma16(const void* g, unsigned lds) {
+  unsigned saved;
+  const unsigned base = __builtin_amdgcn_readfirstlane(lds);
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(saved)
+               : "v"(g), "s"(base)
+               : "memory");
+}
+
+// at most N of this wave's vector-memory ops outstanding (its DMA of the stage about to be read
+// has landed), LDS ops retired, then the workgroup barrier. Any N < 64: the count is an assembler
+// immediate (an earlier form with one asm string per count fell back to vmcnt(0) for every count
+// it did not list). sched_barrier(0) on both sides: register-only MFMAs would otherwise migrate
+// across the asm statement, which only orders memory operations.
+template <int N>
+__device__ __forceinline__ void ha_wait_barrier() {
+  static_assert(N >= 0 && N < 64, "vmcnt range");
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"(N) : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// the counted wait alone
+template <int N>
+__device__ __forceinline__ void ha_vm_wait() {
+  static_assert(N >= 0 && N < 64, "vmcnt range");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
+}
+
 // Inter-workgroup hand-off inside one launch without a per-block release fence (the
 // "write-through stores + counter" form of the CDNA4 visibility rules): every handed-off word is
 // stored sc1 (relaxed agent-scope atomic store on a GLOBAL pointer), every storing wave drains

@@ -8,29 +8,18 @@
 //   * 128 x 128 output tile, 4 waves of 64 x 64 = 4 x 4 accumulator blocks of 16 x 16 (64 doubles
 //     = 128 registers per lane), two workgroups per CU so one tile's epilogue / prologue overlaps
 //     the other's MFMAs;
-//   * operands global -> LDS by asm LDS-DMA (global_load_lds_dwordx4, 1 KB per wave-instruction)
-//     into a ring of 4 stage buffers of 8 k (16 KB per stage: 8 pieces per operand, 2 + 2 per
-//     wave; 64 KB per workgroup), 3 stages in flight behind a COUNTED vmcnt and one raw s_barrier
-//     per stage - never vmcnt(0) in the steady state;
+//   * operands global -> LDS through the 4-slot staging ring (64 KB per workgroup) that f64_ring.h
+//     describes: the pipeline, both operand images, the K tail and the read behind an odd K;
 //   * fragments of stage t + 1 are read into the second register set between stage t's MFMAs;
 //   * f64 fragment map: lane -> row lane & 15, k-slot lane >> 4. A stage is two MFMA k-steps
 //     s = 0, 1; k-slot kk of step s holds the stage's k = 2 kk + s, for A and B alike:
-//       - k-contiguous operand: image [k/2][row][2] (one 16-byte DMA lane = two consecutive k of one
-//         row); a lane reads its row's pair kk with ONE ds_read_b128 and feeds both steps - 16
-//         lanes read 256 contiguous bytes, conflict-free;
-//       - row-contiguous operand: image [k][row] (one piece = one whole k-row of 128 rows). The
-//         rows of each pair of 16 x 16 blocks are INTERLEAVED - block 2 p + j, lane r <-> wave row
-//         32 p + 2 r + j - so one ds_read_b128 at k-row 2 kk + s feeds two blocks (again 256
-//         contiguous bytes per 16 lanes); the epilogue maps rows / columns back;
-//   * out-of-range rows / columns are clamped at the load and masked at the store; the K tail is
-//     clamped and zeroed in LDS after it lands; K may be odd: the 16-byte load of the last pair
-//     then also takes the 8 bytes behind k = K - 1 and zeroes them like the rest of the tail. In
-//     every row but the last these lie inside the (even) leading dimension. In the very last row
-//     of a tensor whose storage ends exactly at its last element they are OUT OF THE ALLOCATION:
-//     the kernel reads them on purpose. The read cannot fault - the load is 16-byte aligned and
-//     its first half is in bounds, so it stays inside that element's page - and its value never
-//     reaches a result. The same holds for an odd row count of a row-contiguous operand (the
-//     last k-row's last pair). A memory checker that tracks allocation bounds will report it;
+//       - k-contiguous operand: a lane reads its row's pair kk with ONE ds_read_b128 and feeds
+//         both steps;
+//       - row-contiguous operand: the rows of each pair of 16 x 16 blocks are INTERLEAVED - block
+//         2 p + j, lane r <-> wave row 32 p + 2 r + j - so one ds_read_b128 at k-row 2 kk + s feeds
+//         two blocks (again 256 contiguous bytes per 16 lanes); the epilogue maps rows / columns
+//         back;
+//   * out-of-range rows / columns are clamped at the load and masked at the store;
 //   * 1-D grid in the XCD-aware grouped tile order of gemm_f32m (up to 2^31 - 1 tiles), split-K
 //     slices on blockIdx.y into fp64 partials, summed in slice order by fd_sum_slices (bit-identical
 //     run to run, no atomics); "upper": tiles wholly below the diagonal return at once and only
@@ -51,86 +40,15 @@
 // stage / one workgroup per CU alternative was not built: with an f64 MFMA of 64 cycles a stage is
 // 2048 MFMA cycles per wave against 8 LDS reads and 4 DMAs, so the tile's prologue and epilogue,
 // which only a second workgroup can hide, are what is left to overlap.
-#include "common.h"
+#include "f64_ring.h"
 
 #include <type_traits>
 
 namespace {
 
-typedef double doublex2 __attribute__((ext_vector_type(2)));
-typedef double doublex4 __attribute__((ext_vector_type(4)));
-
-constexpr int FT = 128;             // tile rows / columns
-constexpr int FK = 8;               // k per stage
-constexpr int FOP = FT * FK * 8;    // bytes per operand per stage
-constexpr int FSTG = 2 * FOP;       // bytes per stage
+constexpr int FT = F64_T;           // tile rows / columns
 constexpr int FNBUF = 4;            // ring slots
 constexpr int FAHEAD = FNBUF - 1;   // stages in flight
-constexpr int FDPS = 4;             // DMA instructions per wave per stage (2 of A, 2 of B)
-
-// 32-bit: the host caps the grid at 2^31 - 1 tiles
-__device__ __forceinline__ unsigned fd_xcd_remap(unsigned orig, unsigned nwg) {
-  const unsigned q = nwg / 8, r = nwg % 8, xcd = orig % 8, loc = orig / 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-}
-
-// LDS-DMA of 16 bytes per lane to LDS byte address lds + 16 lane (wave-uniform lds); M0 saved /
-// restored around it (the compiler treats M0 as reserved and would not see a clobber)
-__device__ __forceinline__ void fd_dma16(const void* g, unsigned lds) {
-  unsigned saved;
-  const unsigned base = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(saved)
-               : "v"(g), "s"(base)
-               : "memory");
-}
-
-// at most N of this wave's vector-memory ops outstanding, LDS ops retired, then the barrier
-template <int N>
-__device__ __forceinline__ void fd_wait_barrier() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// One operand's staging for this lane. KC (k-contiguous, [rows][K] with leading dimension ld):
-// piece q = k-pair q / 2 of the stage, rows 64 (q % 2) + lane. Else row-contiguous ([K][rows]):
-// piece q = k-row q, rows 2 lane, 2 lane + 1. Either way piece q lands at byte q KB of the
-// operand's image. Out-of-range rows are clamped (their results are masked at the store).
-template <bool KC>
-struct FdSrc {
-  const double* p0;  // KC: row lane of the tile; else rows 2 lane .. + 1 at k = 0
-  const double* p1;  // KC: row 64 + lane
-  int64_t ld;
-  __device__ __forceinline__ void init(const double* P, int64_t ld_, int64_t rows, int64_t r0, int lane) {
-    ld = ld_;
-    if (KC) {
-      const int64_t a = r0 + lane, b = r0 + 64 + lane;
-      p0 = P + (a < rows ? a : rows - 1) * ld;
-      p1 = P + (b < rows ? b : rows - 1) * ld;
-    } else {
-      const int64_t c = r0 + 2 * lane, last = (rows - 1) & ~(int64_t)1;
-      p0 = p1 = P + (c < last ? c : last);
-    }
-  }
-  // source of piece q of the stage at k0 (whole stage in range)
-  __device__ __forceinline__ const double* src(int64_t k0, int q) const {
-    return KC ? ((q & 1) ? p1 : p0) + k0 + 2 * (q >> 1) : p0 + (k0 + q) * ld;
-  }
-  // the same with k clamped into the operand (the tail stage; entries at k >= K are zeroed after
-  // they land)
-  __device__ __forceinline__ const double* src_clamped(int64_t k0, int q, int64_t K) const {
-    if (KC) {
-      const int64_t k = k0 + 2 * (q >> 1), last = (K - 1) & ~(int64_t)1;
-      return ((q & 1) ? p1 : p0) + (k < last ? k : last);
-    }
-    const int64_t k = k0 + q;
-    return p0 + (k < K ? k : K - 1) * ld;
-  }
-  // first k of piece q's two values (KC: k, k + 1; else both values at this k)
-  __device__ __forceinline__ int64_t kfirst(int64_t k0, int q) const { return KC ? k0 + 2 * (q >> 1) : k0 + q; }
-};
 
 // Fragments of one stage for a wave: a[b][s], b[b][s] = block b's operand for MFMA k-step s.
 struct FdFrag {
@@ -139,55 +57,55 @@ struct FdFrag {
 
 // AK: A k-major ([K][M], m contiguous) - else row-major ([M][K], k contiguous).
 // BK_: B k-major ([K][N], n contiguous) - else n-major ([N][K], k contiguous).
-// Split-K: slice blockIdx.y covers k in [y kps FK, min((y + 1) kps FK, K)) and writes C + y cslice.
+// Split-K: slice blockIdx.y covers k in [y kps 8, min((y + 1) kps 8, K)) and writes C + y cslice.
 template <bool AK, bool BK_>
 __global__ __launch_bounds__(256, 2) void gemm_f64k(const double* __restrict__ A, const double* __restrict__ B,
                                                     double* __restrict__ C, int64_t M, int64_t N, int64_t K,
                                                     int64_t lda, int64_t ldb, int64_t ldc, double alpha, int beta,
                                                     int upper, int64_t kps, int64_t cslice) {
-  static_assert(FNBUF * FSTG <= 80 * 1024, "two workgroups per CU");
-  __shared__ __attribute__((aligned(16))) unsigned char smem[FNBUF * FSTG];
+  static_assert(FNBUF * F64_STG <= 80 * 1024, "two workgroups per CU");
+  __shared__ __attribute__((aligned(16))) unsigned char smem[FNBUF * F64_STG];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int kk = lane >> 4, r = lane & 15;
   const unsigned tn = (unsigned)((N + FT - 1) / FT), tm = (unsigned)((M + FT - 1) / FT);
-  const unsigned bid = fd_xcd_remap(blockIdx.x, tm * tn);
+  const unsigned bid = ha_xcd_remap(blockIdx.x, tm * tn);
   constexpr unsigned GM = 8;
   const unsigned grp = bid / (GM * tn), gfirst = grp * GM;
   const unsigned gsz = tm - gfirst < GM ? tm - gfirst : GM;
   const int64_t m0 = (int64_t)(gfirst + (bid % (GM * tn)) % gsz) * FT, n0 = (int64_t)((bid % (GM * tn)) / gsz) * FT;
   if (upper && n0 + FT <= m0) return;  // wholly below the diagonal (workgroup-uniform, before any barrier)
   {
-    const int64_t k0 = (int64_t)blockIdx.y * kps * FK;
+    const int64_t k0 = (int64_t)blockIdx.y * kps * F64_K;
     A += AK ? k0 * lda : k0;
     B += BK_ ? k0 * ldb : k0;
-    K = K - k0 < kps * FK ? K - k0 : kps * FK;
+    K = K - k0 < kps * F64_K ? K - k0 : kps * F64_K;
     C += (int64_t)blockIdx.y * cslice;
   }
-  FdSrc<!AK> sa;
-  FdSrc<!BK_> sb;
+  F64Src<!AK> sa;
+  F64Src<!BK_> sb;
   sa.init(A, lda, M, m0, lane);
   sb.init(B, ldb, N, n0, lane);
   const unsigned sbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
 
   auto stage = [&](int64_t t, bool full) {
-    const unsigned dst = sbase + (unsigned)((t % FNBUF) * FSTG);
-    const int64_t k0 = t * FK;
+    const unsigned dst = sbase + (unsigned)((t % FNBUF) * F64_STG);
+    const int64_t k0 = t * F64_K;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = 2 * wave + i;
-      fd_dma16(full ? sa.src(k0, q) : sa.src_clamped(k0, q, K), dst + q * 1024);
+      ha_dma16(full ? sa.src(k0, q) : sa.src_clamped(k0, q, K), dst + q * 1024);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = 2 * wave + i;
-      fd_dma16(full ? sb.src(k0, q) : sb.src_clamped(k0, q, K), dst + FOP + q * 1024);
+      ha_dma16(full ? sb.src(k0, q) : sb.src_clamped(k0, q, K), dst + F64_OP + q * 1024);
     }
   };
   // this wave's own pieces of the tail stage: the values at k >= K become zero
   auto zero_tail = [&](int64_t t) {
-    unsigned char* dst = smem + (t % FNBUF) * FSTG;
-    const int64_t k0 = t * FK;
+    unsigned char* dst = smem + (t % FNBUF) * F64_STG;
+    const int64_t k0 = t * F64_K;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = 2 * wave + i;
@@ -195,7 +113,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64k(const double* __restrict__ A
       const int64_t ka = sa.kfirst(k0, q);
       if (ka >= K) pa[0] = 0.0;
       if (ka + (AK ? 0 : 1) >= K) pa[1] = 0.0;
-      double* pb = reinterpret_cast<double*>(dst + FOP + q * 1024 + lane * 16);
+      double* pb = reinterpret_cast<double*>(dst + F64_OP + q * 1024 + lane * 16);
       const int64_t kb = sb.kfirst(k0, q);
       if (kb >= K) pb[0] = 0.0;
       if (kb + (BK_ ? 0 : 1) >= K) pb[1] = 0.0;
@@ -224,9 +142,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f64k(const double* __restrict__ A
     }
   };
   auto load = [&](FdFrag& F, int64_t t) {
-    const unsigned char* base = smem + (t % FNBUF) * FSTG;
+    const unsigned char* base = smem + (t % FNBUF) * F64_STG;
     opnd(base, wm * 64, std::integral_constant<bool, !AK>(), F.a);
-    opnd(base + FOP, wn * 64, std::integral_constant<bool, !BK_>(), F.b);
+    opnd(base + F64_OP, wn * 64, std::integral_constant<bool, !BK_>(), F.b);
   };
 
   // accumulator (block bm, bn) element g <-> tile row / column: the f64 16x16x4 C/D map is
@@ -254,18 +172,18 @@ __global__ __launch_bounds__(256, 2) void gemm_f64k(const double* __restrict__ A
           acc[bm][bn] = __builtin_amdgcn_mfma_f64_16x16x4f64(F.a[bm][s], F.b[bn][s], acc[bm][bn], 0, 0, 0);
   };
 
-  const int64_t nk = K > 0 ? (K + FK - 1) / FK : 0;
-  const bool tail = (K % FK) != 0;
+  const int64_t nk = K > 0 ? (K + F64_K - 1) / F64_K : 0;
+  const bool tail = (K % F64_K) != 0;
   // stage t landed (this wave's DMA) and visible to every wave; later stages may be in flight
   auto ready = [&](int64_t t) {
     const int64_t later = nk - 1 - t < FAHEAD - 1 ? nk - 1 - t : FAHEAD - 1;  // stages issued after t
     if (tail && t == nk - 1) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      ha_vm_wait<0>();
       zero_tail(t);
     }
-    if (later >= 2) fd_wait_barrier<2 * FDPS>();
-    else if (later == 1) fd_wait_barrier<FDPS>();
-    else fd_wait_barrier<0>();
+    if (later >= 2) ha_wait_barrier<2 * F64_DPS>();
+    else if (later == 1) ha_wait_barrier<F64_DPS>();
+    else ha_wait_barrier<0>();
   };
   // steady state: stage t + AHEAD issued (whole, in range), the first half of the MFMAs around
   // it, the counted wait for stage t + 1 + barrier, then stage t + 1's fragment reads between the
@@ -274,7 +192,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64k(const double* __restrict__ A
     stage(t + FAHEAD, true);
     mma_half(Fc, 0);
     __builtin_amdgcn_sched_barrier(0);
-    fd_wait_barrier<(FAHEAD - 1) * FDPS>();
+    ha_wait_barrier<(FAHEAD - 1) * F64_DPS>();
     load(Fn, t + 1);
     mma_half(Fc, 1);
     __builtin_amdgcn_sched_barrier(0);
@@ -390,7 +308,7 @@ int f64_launch(const double* A, const double* B, double* C, int64_t M, int64_t N
 
 // the slice count a request for `slices` becomes: ceil(nk / ceil(nk / slices)) over nk 8-k stages
 int64_t f64_norm_slices(int64_t K, int64_t slices) {
-  const int64_t nk = (K + FK - 1) / FK;
+  const int64_t nk = (K + F64_K - 1) / F64_K;
   if (nk <= 0 || slices <= 1) return 1;
   if (slices > 65535) slices = 65535;
   const int64_t kps = (nk + slices - 1) / slices;
@@ -444,7 +362,7 @@ HA_EXPORT int ha_gemm_f64(const double* A, const double* B, double* C, int64_t M
   }
   const int64_t tiles = ((M + FT - 1) / FT) * ((N + FT - 1) / FT);
   if (tiles > 0x7fffffffLL) return HA_UNSUPPORTED;
-  const int64_t nk = (K + FK - 1) / FK;
+  const int64_t nk = (K + F64_K - 1) / F64_K;
   const int64_t ns = P ? f64_norm_slices(K, slices) : 1;
   const int64_t kps = (nk + ns - 1) / ns;
   double* dst = ns > 1 ? P : C;

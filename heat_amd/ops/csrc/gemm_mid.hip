@@ -43,39 +43,6 @@ constexpr int MK = 16;        // k per stage
 constexpr int MOP = 8192;     // bytes per operand per stage (128 rows x 16 k x 4 B)
 constexpr int MSTAGE = 2 * MOP;
 
-// 32-bit: the host caps the grid at 2^31 tiles (64-bit divisions are long SALU sequences)
-__device__ __forceinline__ unsigned gm_xcd_remap(unsigned orig, unsigned nwg) {
-  const unsigned q = nwg / 8, r = nwg % 8, xcd = orig % 8, loc = orig / 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-}
-
-// LDS-DMA of 16 bytes per lane to LDS byte address lds + 16 lane (wave-uniform lds); M0 saved /
-// restored around it (the compiler treats M0 as reserved and would not see a clobber)
-__device__ __forceinline__ void gm_dma16(const void* g, unsigned lds) {
-  unsigned saved;
-  const unsigned base = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(saved)
-               : "v"(g), "s"(base)
-               : "memory");
-}
-
-// at most N of this wave's vector-memory ops outstanding, LDS ops retired, then the barrier (any
-// N < 64: the count is an assembler immediate; an earlier three-case form fell back to vmcnt(0)
-// for the counts of the 256 x 128 variant, 12 and 6)
-template <int N>
-__device__ __forceinline__ void gm_wait_barrier() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-template <int N>
-__device__ __forceinline__ void gm_vm_wait() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
 // One operand's staging for this lane, TR tile rows (128 or 256). KC (k-contiguous, [rows][K]
 // with leading dimension ld): G = TR / 64 row groups; piece q = k-chunk q / G (4 k), rows
 // 64 (q % G) + lane; image [4 chunks][TR rows][4] - piece q at q KB. Else row-contiguous ([K][rows]):
@@ -155,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32m(const float* __restrict__ A,
   const int wm = wave >> 1, wn = wave & 1;
   const int h = lane >> 5, r = lane & 31;
   const unsigned tn = (unsigned)((N + TN - 1) / TN), tm = (unsigned)((M + TM - 1) / TM);
-  const unsigned bid = gm_xcd_remap(blockIdx.x, tm * tn);
+  const unsigned bid = ha_xcd_remap(blockIdx.x, tm * tn);
   constexpr unsigned GM = 8;
   const unsigned grp = bid / (GM * tn), gfirst = grp * GM;
   const unsigned gsz = tm - gfirst < GM ? tm - gfirst : GM;
@@ -180,12 +147,12 @@ __global__ __launch_bounds__(256, 2) void gemm_f32m(const float* __restrict__ A,
 #pragma unroll
     for (int i = 0; i < PAW; ++i) {
       const int q = PAW * wave + i;
-      gm_dma16(full ? sa.src(k0, q) : sa.src_clamped(k0, q, K, lane), dst + q * 1024);
+      ha_dma16(full ? sa.src(k0, q) : sa.src_clamped(k0, q, K, lane), dst + q * 1024);
     }
 #pragma unroll
     for (int i = 0; i < PBW; ++i) {
       const int q = PBW * wave + i;
-      gm_dma16(full ? sb.src(k0, q) : sb.src_clamped(k0, q, K, lane), dst + AOP + q * 1024);
+      ha_dma16(full ? sb.src(k0, q) : sb.src_clamped(k0, q, K, lane), dst + AOP + q * 1024);
     }
   };
   auto zero_tail = [&](int64_t t) {
@@ -292,12 +259,12 @@ __global__ __launch_bounds__(256, 2) void gemm_f32m(const float* __restrict__ A,
   auto ready = [&](int64_t t) {
     const int64_t later = nk - 1 - t < AHEAD - 1 ? nk - 1 - t : AHEAD - 1;  // stages issued after t
     if (tail && t == nk - 1) {
-      gm_vm_wait<0>();
+      ha_vm_wait<0>();
       zero_tail(t);
     }
-    if (later >= 2) gm_wait_barrier<2 * DPS>();
-    else if (later == 1) gm_wait_barrier<DPS>();
-    else gm_wait_barrier<0>();
+    if (later >= 2) ha_wait_barrier<2 * DPS>();
+    else if (later == 1) ha_wait_barrier<DPS>();
+    else ha_wait_barrier<0>();
   };
   // steady state: stage t + AHEAD issued (whole, in range), MFMAs of the first half of the block
   // rows around it, the counted wait for stage t + 1 + barrier, then stage t + 1's fragment reads
@@ -311,7 +278,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32m(const float* __restrict__ A,
       __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);              // VMEM read (the asm DMA)
     }
     __builtin_amdgcn_sched_barrier(0);
-    gm_wait_barrier<(AHEAD - 1) * DPS>();
+    ha_wait_barrier<(AHEAD - 1) * DPS>();
     load(Fn, t + 1);
     mma_half(Fc, 1);
     __builtin_amdgcn_sched_barrier(0);
@@ -339,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32m(const float* __restrict__ A,
     for (int64_t t = 0; t < nk; t += 2) {
       // stages t, t + 1 are this wave's only DMAs in flight: landed, and past the barrier every
       // wave has landed its pieces and finished reading stages t - 2, t - 1 (the slots refilled now)
-      gm_wait_barrier<0>();
+      ha_wait_barrier<0>();
       load(F0, t);
       const bool more = t + 2 < nk;
       if (more) stage(t + 2, true);

@@ -70,24 +70,11 @@ __device__ __forceinline__ void tg_dma16(const void* src, unsigned char* dst) {
   __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
 }
 
-// wait until at most N of this wave's vector-memory ops are outstanding (its DMA of the stage
-// about to be read has landed), retire LDS ops, then the workgroup barrier
-// (sched_barrier(0) on both sides: register-only MFMAs would otherwise migrate across the
-// asm statement, which only orders memory operations)
-template <int N>
-__device__ __forceinline__ void tg_wait_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 __device__ __forceinline__ void tg_wait_stage(int64_t t, int64_t nk) {
   // stage t has landed; stages t+1, t+2 (when they exist) may still be in flight (8 DMA per stage)
-  if (t + 2 < nk) tg_wait_barrier<16>();
-  else if (t + 1 < nk) tg_wait_barrier<8>();
-  else tg_wait_barrier<0>();
+  if (t + 2 < nk) ha_wait_barrier<16>();
+  else if (t + 1 < nk) ha_wait_barrier<8>();
+  else ha_wait_barrier<0>();
 }
 
 
@@ -224,7 +211,7 @@ __global__ __launch_bounds__(256, 1) void gemm_h3t(const _Float16* __restrict__ 
       __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);  // VMEM (LDS-DMA)
     }
     __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-    tg_wait_barrier<16>();
+    ha_wait_barrier<16>();
     load(Fn, t + 1);
     mma_row(Fc, 1);
     mma_row(Fc, 2);
@@ -624,7 +611,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f32t(const float* __restrict__ A_
       __builtin_amdgcn_sched_group_barrier(0x008, MI16 ? 8 : 4, 0);
       __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
     }
-    tg_wait_barrier<16>();
+    ha_wait_barrier<16>();
     load(Fn, t + 1);
     mma_part(Fc, 1);
     mma_part(Fc, 2);

@@ -7,11 +7,8 @@
 //
 // km64_assign: label(i) = argmin_j s(i, j), s(i, j) = |c_j|^2 - 2 x_i.c_j, ties to the lowest j.
 //   * one 4-wave workgroup owns 128 points and walks the centroids in tiles of 128; per centroid
-//     tile the feature loop of cdist_f64.hip's cdist_f64_mm runs unchanged: both operands
-//     k-contiguous in the [k/2][row][2] LDS image, asm LDS-DMA into a ring of 4 stages of 8
-//     features (16 KB each), 3 in flight behind a counted vmcnt, one raw s_barrier per stage; the
-//     tail stage is clamped at the load and zeroed in LDS; any f >= 1 (fewer stages than the ring,
-//     f no multiple of 8, odd f) takes the same guarded steps;
+//     tile the features of both (k-contiguous) operands come through the 4-slot staging ring that
+//     f64_ring.h describes (pipeline, tail, what any f >= 1 means for the loads);
 //   * the CENTROIDS feed the MFMA's A side and the points the B side. Under the f64 16x16x4 C/D map
 //     (column = lane & 15, row = (lane >> 4) + 4 g) a lane then owns ONE point and 4 centroids per
 //     accumulator block, so the per-tile argmin is in-lane. A wave takes 32 points x all 128
@@ -22,10 +19,9 @@
 //     so the only cross-lane step is ONE lexicographic (score, index) merge over the 4 lane groups
 //     (xor 16, 32) after the last tile. Every score is one MFMA chain over the features in index
 //     order plus one fma with |c_j|^2: it depends neither on n nor on the tile the point is in;
-//   * |c|^2 comes from km64_norms (16 lanes per row, lane l sums features l, l + 16, ... in order,
-//     then a fixed xor tree) into k doubles of workspace, read per tile in the in-lane argmin
-//     (L2 hits); |x|^2 is computed by the same pre-pass only when the distance is asked for:
-//     mind = max(0, |x|^2 + best);
+//   * |c|^2 comes from f64_row_norms (f64_ring.h) into k doubles of workspace, read per tile in
+//     the in-lane argmin (L2 hits); |x|^2 is computed by the same pre-pass only when the distance
+//     is asked for: mind = max(0, |x|^2 + best);
 //   * out-of-range points are clamped at the load and never stored; out-of-range centroids are
 //     clamped at the load and scored +inf. Small k (the k = 8 of the reference benchmark) runs the
 //     same kernel with masked centroid columns;
@@ -33,14 +29,13 @@
 //     __syncthreads separates two tiles' rings.
 //   Not built: keeping the workgroup's X tile resident in LDS where 128 x f doubles fit beside the
 //   ring (f <= 16 at two workgroups per CU), and a narrow-k variant for k < 128.
-//   Requirements (made so by the Python wrapper, never by a copy in here): 16-byte aligned X, C with
-//   even leading dimensions; for odd f the 16-byte load of the last pair also takes the 8 bytes
-//   behind feature f - 1, which must be readable (they are zeroed in LDS). 64-bit offsets.
+//   Requirements (made so by the Python wrapper, never by a copy in here): the ring's, on X and C.
+//   64-bit offsets.
 //
 // Compile figures (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage):
 //   kernel           VGPRs  AGPRs  SGPRs  LDS bytes  scratch  occupancy (waves / SIMD)
 //   km64_assign<*>    254      0    106     65536        0       2
-//   km64_norms         12      0     20         0        0       8
+//   f64_row_norms      12      0     20         0        0       8
 //   (kmeans.hip)  ku_gather_det_f64<true / false>  90 / 76 VGPRs, no LDS, no scratch, 5 / 6 waves;
 //   ku_reduce_det_f64 36 VGPRs, 8 waves; (kmeans_finalize.hip) km_finalize<double, double> 20 VGPRs.
 // 2 waves per SIMD = two workgroups per CU. The stage's fragment reads are split (point blocks and
@@ -75,79 +70,16 @@
 // k = 1024 it is matrix-core work: 2 n k f = 1.05 TFLOP in 17.7 ms at f = 128 = 59 TF of fp64 MFMA,
 // and 26 TF at f = 18, where each 128-centroid tile pays its own ring prologue and drain for three
 // stages. Overlapping a tile's prologue with the previous tile's argmin was not tried.
-#include "common.h"
+#include "f64_ring.h"
 
 #include <cmath>
 
 namespace {
 
-typedef double doublex2 __attribute__((ext_vector_type(2)));
-typedef double doublex4 __attribute__((ext_vector_type(4)));
-
-// ------------------------------------------------------------------------------------- row norms
-// out[i] = |row i|^2 for the rows of C (i < k) then of X (i - k < n; n = 0: C only)
-__global__ __launch_bounds__(256) void km64_norms(const double* __restrict__ C, int64_t k, int64_t ldc,
-                                                  const double* __restrict__ X, int64_t n, int64_t ldx, int64_t f,
-                                                  double* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-  const int l = threadIdx.x & 15;
-  if (i >= k + n) return;  // whole 16-lane groups leave together
-  const double* row = i < k ? C + i * ldc : X + (i - k) * ldx;
-  double s = 0.0;
-  for (int64_t j = l; j < f; j += 16) s = fma(row[j], row[j], s);
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
-  if (l == 0) out[i] = s;
-}
-
 // ------------------------------------------------------------------------------ fused assignment
-constexpr int KT = 128;            // points per workgroup / centroids per tile
-constexpr int KK = 8;              // features per stage
-constexpr int KOP = KT * KK * 8;   // bytes per operand per stage
-constexpr int KSTG = 2 * KOP;      // bytes per stage
+constexpr int KT = F64_T;          // points per workgroup / centroids per tile
 constexpr int KNBUF = 4;           // ring slots
 constexpr int KAHEAD = KNBUF - 1;  // stages in flight
-constexpr int KDPS = 4;            // DMA instructions per wave per stage (2 per operand)
-
-// LDS-DMA of 16 bytes per lane to LDS byte address lds + 16 lane (wave-uniform lds); M0 saved /
-// restored around it (the compiler treats M0 as reserved and would not see a clobber)
-__device__ __forceinline__ void km64_dma16(const void* g, unsigned lds) {
-  unsigned saved;
-  const unsigned base = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(saved)
-               : "v"(g), "s"(base)
-               : "memory");
-}
-
-// at most N of this wave's vector-memory ops outstanding, LDS ops retired, then the barrier
-template <int N>
-__device__ __forceinline__ void km64_wait_barrier() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// One operand's staging for this lane: piece q of a stage = feature pair q / 2, tile rows
-// 64 (q % 2) + lane, landing at byte q KB of the operand's image. Out-of-range rows are clamped.
-struct Km64Src {
-  const double* p0;  // tile row lane
-  const double* p1;  // tile row 64 + lane
-  __device__ __forceinline__ void init(const double* P, int64_t ld, int64_t rows, int64_t r0, int lane) {
-    const int64_t a = r0 + lane, b = r0 + 64 + lane;
-    p0 = P + (a < rows ? a : rows - 1) * ld;
-    p1 = P + (b < rows ? b : rows - 1) * ld;
-  }
-  __device__ __forceinline__ const double* src(int64_t k0, int q) const {
-    return ((q & 1) ? p1 : p0) + k0 + 2 * (q >> 1);
-  }
-  // the tail stage: the pair clamped into the row (entries at k >= f are zeroed after they land)
-  __device__ __forceinline__ const double* src_clamped(int64_t k0, int q, int64_t f) const {
-    const int64_t k = k0 + 2 * (q >> 1), last = (f - 1) & ~(int64_t)1;
-    return ((q & 1) ? p1 : p0) + (k < last ? k : last);
-  }
-};
 
 // Fragments of one stage for a wave: c[b][s] = centroid block b (A side), x[b][s] = point block b
 // (B side) for MFMA k-step s.
@@ -161,40 +93,40 @@ __global__ __launch_bounds__(256, 2) void km64_assign(const double* __restrict__
                                                       int64_t ldx, int64_t ldc, const double* __restrict__ cn,
                                                       const double* __restrict__ xn, int* __restrict__ labels,
                                                       double* __restrict__ mind) {
-  static_assert(KNBUF * KSTG <= 80 * 1024, "two workgroups per CU");
-  __shared__ __attribute__((aligned(16))) unsigned char smem[KNBUF * KSTG];
+  static_assert(KNBUF * F64_STG <= 80 * 1024, "two workgroups per CU");
+  __shared__ __attribute__((aligned(16))) unsigned char smem[KNBUF * F64_STG];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kk = lane >> 4, r = lane & 15;
   const int64_t x0 = (int64_t)blockIdx.x * KT;
 
-  Km64Src sc, sx;
+  F64Src<> sc, sx;
   sx.init(X, ldx, n, x0, lane);
   const unsigned sbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
 
   // the centroids' image first, the points' behind it
   auto stage = [&](int64_t t, bool full) {
-    const unsigned dst = sbase + (unsigned)((t % KNBUF) * KSTG);
-    const int64_t k0 = t * KK;
+    const unsigned dst = sbase + (unsigned)((t % KNBUF) * F64_STG);
+    const int64_t k0 = t * F64_K;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = 2 * wave + i;
-      km64_dma16(full ? sc.src(k0, q) : sc.src_clamped(k0, q, f), dst + q * 1024);
+      ha_dma16(full ? sc.src(k0, q) : sc.src_clamped(k0, q, f), dst + q * 1024);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = 2 * wave + i;
-      km64_dma16(full ? sx.src(k0, q) : sx.src_clamped(k0, q, f), dst + KOP + q * 1024);
+      ha_dma16(full ? sx.src(k0, q) : sx.src_clamped(k0, q, f), dst + F64_OP + q * 1024);
     }
   };
   // this wave's own pieces of the tail stage: the values at k >= f become zero
   auto zero_tail = [&](int64_t t) {
-    unsigned char* dst = smem + (t % KNBUF) * KSTG;
-    const int64_t ka = t * KK + 2 * wave;  // both of this wave's pieces hold the pair ka, ka + 1
+    unsigned char* dst = smem + (t % KNBUF) * F64_STG;
+    const int64_t ka = t * F64_K + 2 * wave;  // both of this wave's pieces hold the pair ka, ka + 1
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = 2 * wave + i;
       double* pa = reinterpret_cast<double*>(dst + q * 1024 + lane * 16);
-      double* pb = reinterpret_cast<double*>(dst + KOP + q * 1024 + lane * 16);
+      double* pb = reinterpret_cast<double*>(dst + F64_OP + q * 1024 + lane * 16);
       if (ka >= f) pa[0] = pb[0] = 0.0;
       if (ka + 1 >= f) pa[1] = pb[1] = 0.0;
     }
@@ -203,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void km64_assign(const double* __restrict__
   // fragment reads: all 8 centroid blocks, the wave's 2 point blocks; lane's row r within a block
   // in two parts: the point blocks and centroid blocks 0-3 (part 0), centroid blocks 4-7 (part 1)
   auto load = [&](Km64Frag& F, int64_t t, int part) {
-    const unsigned char* base = smem + (t % KNBUF) * KSTG + kk * (KT * 16) + r * 16;
+    const unsigned char* base = smem + (t % KNBUF) * F64_STG + kk * (KT * 16) + r * 16;
 #pragma unroll
     for (int b = 4 * part; b < 4 * part + 4; ++b) {
       const doublex2 v = *reinterpret_cast<const doublex2*>(base + (16 * b) * 16);
@@ -213,7 +145,7 @@ __global__ __launch_bounds__(256, 2) void km64_assign(const double* __restrict__
     if (part) return;
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-      const doublex2 v = *reinterpret_cast<const doublex2*>(base + KOP + (32 * wave + 16 * b) * 16);
+      const doublex2 v = *reinterpret_cast<const doublex2*>(base + F64_OP + (32 * wave + 16 * b) * 16);
       F.x[b][0] = v[0];
       F.x[b][1] = v[1];
     }
@@ -232,18 +164,18 @@ __global__ __launch_bounds__(256, 2) void km64_assign(const double* __restrict__
           acc[bm][bn] = __builtin_amdgcn_mfma_f64_16x16x4f64(F.c[bm][s], F.x[bn][s], acc[bm][bn], 0, 0, 0);
   };
 
-  const int64_t nk = (f + KK - 1) / KK;
-  const bool tail = (f % KK) != 0;
+  const int64_t nk = (f + F64_K - 1) / F64_K;
+  const bool tail = (f % F64_K) != 0;
   // stage t landed (this wave's DMA) and visible to every wave; later stages may be in flight
   auto ready = [&](int64_t t) {
     const int64_t later = nk - 1 - t < KAHEAD - 1 ? nk - 1 - t : KAHEAD - 1;  // stages issued after t
     if (tail && t == nk - 1) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      ha_vm_wait<0>();
       zero_tail(t);
     }
-    if (later >= 2) km64_wait_barrier<2 * KDPS>();
-    else if (later == 1) km64_wait_barrier<KDPS>();
-    else km64_wait_barrier<0>();
+    if (later >= 2) ha_wait_barrier<2 * F64_DPS>();
+    else if (later == 1) ha_wait_barrier<F64_DPS>();
+    else ha_wait_barrier<0>();
   };
   // steady state (f >= 40): stage t + AHEAD issued whole, the first half of the MFMAs around it,
   // the counted wait for stage t + 1 + barrier, the first part of stage t + 1's fragment reads
@@ -253,7 +185,7 @@ __global__ __launch_bounds__(256, 2) void km64_assign(const double* __restrict__
     stage(t + KAHEAD, true);
     mma_half(Fc, 0);
     __builtin_amdgcn_sched_barrier(0);
-    km64_wait_barrier<(KAHEAD - 1) * KDPS>();
+    ha_wait_barrier<(KAHEAD - 1) * F64_DPS>();
     load(Fn, t + 1, 0);
     mma_half(Fc, 1);
     __builtin_amdgcn_sched_barrier(0);
@@ -364,7 +296,7 @@ HA_EXPORT int ha_km_assign_f64(const double* X, int64_t n, int64_t f, int64_t ld
   hipStream_t s = (hipStream_t)stream;
   const int64_t nrows = k + (mind ? n : 0);
   if ((nrows + 15) / 16 > 0x7fffffffLL) return HA_UNSUPPORTED;
-  hipLaunchKernelGGL(km64_norms, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, s, C, k, ldc, X,
+  hipLaunchKernelGGL(f64_row_norms, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, s, C, k, ldc, X,
                      mind ? n : (int64_t)0, ldx, f, ws);
   if (ha_launch_status() != HA_OK) return HA_LAUNCH;
   if (mind)

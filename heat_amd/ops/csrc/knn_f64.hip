@@ -9,11 +9,13 @@
 //   * the matrix loop is kmeans_f64.hip's km64_assign: one 4-wave workgroup owns 128 queries and walks
 //     T in tiles of 128 rows on v_mfma_f64_16x16x4_f64; T on the MFMA's A side and Q on the B side, so
 //     a lane owns ONE query per point block (column = lane & 15) and 4 rows of T per accumulator block
-//     (row = (lane >> 4) + 4 g); asm LDS-DMA into a ring of 8-feature stages (16 KB each) behind a
-//     counted vmcnt, one raw s_barrier per stage, the tail stage clamped at the load and zeroed in LDS;
-//     any f >= 1. Every score is one MFMA chain over the features in index order plus one fma with
-//     |t_j|^2 (kn64_norms): it depends neither on nq nor on the tile or the split column, so exactly
-//     duplicated rows of T get bit-identical scores and come out in index order;
+//     (row = (lane >> 4) + 4 g); the features of both operands come through the staging pipeline that
+//     f64_ring.h describes (images, counted waits, tail), here with a templated slot count (3 is no
+//     power of two, so slots are taken by a 32-bit unsigned modulo) and the tail tests behind an opaque
+//     copy of the wave number (below); any f >= 1. Every score is one MFMA chain over the features in
+//     index order plus one fma with |t_j|^2 (f64_row_norms): it depends neither on nq nor on the tile
+//     or the split column, so exactly duplicated rows of T get bit-identical scores and come out in
+//     index order;
 //   * SELECTION. 2 x k register lists of (double, int) per lane do not fit beside 128 accumulator
 //     registers, so the lists live in LDS: per query k sorted (score, index) entries, stored position-
 //     major (entry p of query q at [p][q]: the 16 lanes of a lane group touch 16 neighbouring words).
@@ -42,15 +44,14 @@
 // smallest written as (float64, int64), (+inf, -1) where T has fewer than k rows. This one launch
 // merges the split columns, replaces the expansion scores by exact distances and orders the result.
 //
-// Requirements (made so by the Python wrapper): 16-byte aligned Q, T with even leading dimensions; for
-// odd f the 16-byte load of the last pair also takes the 8 bytes behind feature f - 1, which must be
-// readable (they are zeroed in LDS / not used by the rescoring). 64-bit offsets.
+// Requirements (made so by the Python wrapper): the ring's, on Q and T; the rescoring's 16-byte loads
+// need the same and never take the 8 bytes behind an odd f. 64-bit offsets.
 //
 // Compile figures (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage):
 //   kernel             VGPRs  AGPRs  SGPRs  LDS bytes  scratch  occupancy (waves / SIMD)
 //   kn64_topk<8>        253      0    102     77824        0       2
 //   kn64_topk<16>       256      0     96     73728        0       2
-//   kn64_norms           12      0     18         0        0       8
+//   f64_row_norms        12      0     20         0        0       8
 //   kn64_rescore<*>      28      0   26-30        0        0       8
 // 2 waves per SIMD = two workgroups per CU. Three things kept the lists' code out of scratch: the
 // block's 8 scores stay in two vector values picked through selects on the bits of the (wave-uniform)
@@ -81,81 +82,18 @@
 // columns at k = 16, 8 workgroups on 256 CUs, and the tiles win (1.02 x at f = 18, 1.26 x at f = 128):
 // ht.spatial.cdist_topk sends that class (k > 8, at most two query tiles, >= 2^19 rows) back to them.
 // Not built: a second merge level that would lift the 64-candidate cap of the split columns.
-#include "common.h"
+#include "f64_ring.h"
 
 #include <cmath>
 
 namespace {
 
-typedef double doublex2 __attribute__((ext_vector_type(2)));
-typedef double doublex4 __attribute__((ext_vector_type(4)));
-
-// ------------------------------------------------------------------------------------- row norms
-// out[j] = |row j of T|^2: 16 lanes per row, lane l sums features l, l + 16, ... in order, then a
-// fixed xor tree
-__global__ __launch_bounds__(256) void kn64_norms(const double* __restrict__ T, int64_t nt, int64_t ldt, int64_t f,
-                                                  double* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-  const int l = threadIdx.x & 15;
-  if (i >= nt) return;  // whole 16-lane groups leave together
-  const double* row = T + i * ldt;
-  double s = 0.0;
-  for (int64_t j = l; j < f; j += 16) s = fma(row[j], row[j], s);
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
-  if (l == 0) out[i] = s;
-}
-
 // --------------------------------------------------------------------------------- fused top-k
-constexpr int NT = 128;           // queries per workgroup / rows of T per tile
-constexpr int NK = 8;             // features per stage
-constexpr int NOP = NT * NK * 8;  // bytes per operand per stage
-constexpr int NSTG = 2 * NOP;     // bytes per stage
-constexpr int NDPS = 4;           // DMA instructions per wave per stage (2 per operand)
+constexpr int NT = F64_T;         // queries per workgroup / rows of T per tile
 constexpr int NOIDX = 0x7fffffff; // index of an empty list entry (sorts behind every row)
-
-// LDS-DMA of 16 bytes per lane to LDS byte address lds + 16 lane (wave-uniform lds); M0 saved /
-// restored around it (the compiler treats M0 as reserved and would not see a clobber)
-__device__ __forceinline__ void kn64_dma16(const void* g, unsigned lds) {
-  unsigned saved;
-  const unsigned base = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(saved)
-               : "v"(g), "s"(base)
-               : "memory");
-}
-
-// at most N of this wave's vector-memory ops outstanding, LDS ops retired, then the barrier
-template <int N>
-__device__ __forceinline__ void kn64_wait_barrier() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"i"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 // this wave's LDS writes done and visible to its other lanes; nothing cached across it
 __device__ __forceinline__ void kn64_wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// One operand's staging for this lane: piece q of a stage = feature pair q / 2, tile rows
-// 64 (q % 2) + lane, landing at byte q KB of the operand's image. Out-of-range rows are clamped.
-struct Kn64Src {
-  const double* p0;  // tile row lane
-  const double* p1;  // tile row 64 + lane
-  __device__ __forceinline__ void init(const double* P, int64_t ld, int64_t rows, int64_t r0, int lane) {
-    const int64_t a = r0 + lane, b = r0 + 64 + lane;
-    p0 = P + (a < rows ? a : rows - 1) * ld;
-    p1 = P + (b < rows ? b : rows - 1) * ld;
-  }
-  __device__ __forceinline__ const double* src(int64_t k0, int q) const {
-    return ((q & 1) ? p1 : p0) + k0 + 2 * (q >> 1);
-  }
-  // the tail stage: the pair clamped into the row (entries at k >= f are zeroed after they land)
-  __device__ __forceinline__ const double* src_clamped(int64_t k0, int q, int64_t f) const {
-    const int64_t k = k0 + 2 * (q >> 1), last = (f - 1) & ~(int64_t)1;
-    return ((q & 1) ? p1 : p0) + (k < last ? k : last);
-  }
-};
 
 // Fragments of one stage for a wave: t[b][s] = T block b (A side), q[b][s] = query block b (B side)
 // for MFMA k-step s.
@@ -180,8 +118,8 @@ __global__ __launch_bounds__(256, 2) void kn64_topk(const double* __restrict__ Q
                                                     double* __restrict__ part_s, int* __restrict__ part_i) {
   constexpr int NBUF = KMAX <= 8 ? 4 : 3;  // ring slots
   constexpr int AHEAD = NBUF - 1;          // stages in flight
-  static_assert(NBUF * NSTG + KMAX * NT * 12 <= 80 * 1024, "two workgroups per CU");
-  __shared__ __attribute__((aligned(16))) unsigned char smem[NBUF * NSTG];
+  static_assert(NBUF * F64_STG + KMAX * NT * 12 <= 80 * 1024, "two workgroups per CU");
+  __shared__ __attribute__((aligned(16))) unsigned char smem[NBUF * F64_STG];
   __shared__ double ls[KMAX * NT];  // list scores, [position][query]
   __shared__ int li[KMAX * NT];     // list indices
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -193,37 +131,37 @@ __global__ __launch_bounds__(256, 2) void kn64_topk(const double* __restrict__ Q
   const int64_t tbeg = (int64_t)blockIdx.y * per * NT;
   const int64_t tend = tbeg + per * NT < nt ? tbeg + per * NT : nt;
 
-  Kn64Src st, sq;
+  F64Src<> st, sq;
   sq.init(Q, ldq, nq, q0, lane);
   const unsigned sbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
   auto slot = [](int64_t t) { return (unsigned)t % (unsigned)NBUF; };
 
   // T's image first, the queries' behind it
   auto stage = [&](int64_t t, bool full) {
-    const unsigned dst = sbase + slot(t) * NSTG;
-    const int64_t k0 = t * NK;
+    const unsigned dst = sbase + slot(t) * F64_STG;
+    const int64_t k0 = t * F64_K;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = 2 * wave + i;
-      kn64_dma16(full ? st.src(k0, q) : st.src_clamped(k0, q, f), dst + q * 1024);
+      ha_dma16(full ? st.src(k0, q) : st.src_clamped(k0, q, f), dst + q * 1024);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = 2 * wave + i;
-      kn64_dma16(full ? sq.src(k0, q) : sq.src_clamped(k0, q, f), dst + NOP + q * 1024);
+      ha_dma16(full ? sq.src(k0, q) : sq.src_clamped(k0, q, f), dst + F64_OP + q * 1024);
     }
   };
   // this wave's own pieces of the tail stage: the values at k >= f become zero
   auto zero_tail = [&](int64_t t) {
-    unsigned char* dst = smem + slot(t) * NSTG;
+    unsigned char* dst = smem + slot(t) * F64_STG;
     int w = wave;  // opaque: the two tests below are made here, not hoisted and kept across the tile loop
     asm volatile("" : "+s"(w));
-    const int64_t ka = t * NK + 2 * w;  // both of this wave's pieces hold the pair ka, ka + 1
+    const int64_t ka = t * F64_K + 2 * w;  // both of this wave's pieces hold the pair ka, ka + 1
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int q = 2 * wave + i;
       double* pa = reinterpret_cast<double*>(dst + q * 1024 + lane * 16);
-      double* pb = reinterpret_cast<double*>(dst + NOP + q * 1024 + lane * 16);
+      double* pb = reinterpret_cast<double*>(dst + F64_OP + q * 1024 + lane * 16);
       if (ka >= f) pa[0] = pb[0] = 0.0;
       if (ka + 1 >= f) pa[1] = pb[1] = 0.0;
     }
@@ -232,7 +170,7 @@ __global__ __launch_bounds__(256, 2) void kn64_topk(const double* __restrict__ Q
   // fragment reads: all 8 T blocks, the wave's 2 query blocks; lane's row r within a block, in two
   // parts: the query blocks and T blocks 0-3 (part 0), T blocks 4-7 (part 1)
   auto load = [&](Kn64Frag& F, int64_t t, int part) {
-    const unsigned char* base = smem + slot(t) * NSTG + kk * (NT * 16) + r * 16;
+    const unsigned char* base = smem + slot(t) * F64_STG + kk * (NT * 16) + r * 16;
 #pragma unroll
     for (int b = 4 * part; b < 4 * part + 4; ++b) {
       const doublex2 v = *reinterpret_cast<const doublex2*>(base + (16 * b) * 16);
@@ -242,7 +180,7 @@ __global__ __launch_bounds__(256, 2) void kn64_topk(const double* __restrict__ Q
     if (part) return;
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-      const doublex2 v = *reinterpret_cast<const doublex2*>(base + NOP + (32 * wave + 16 * b) * 16);
+      const doublex2 v = *reinterpret_cast<const doublex2*>(base + F64_OP + (32 * wave + 16 * b) * 16);
       F.q[b][0] = v[0];
       F.q[b][1] = v[1];
     }
@@ -261,18 +199,18 @@ __global__ __launch_bounds__(256, 2) void kn64_topk(const double* __restrict__ Q
           acc[bm][bn] = __builtin_amdgcn_mfma_f64_16x16x4f64(F.t[bm][s], F.q[bn][s], acc[bm][bn], 0, 0, 0);
   };
 
-  const int64_t nk = (f + NK - 1) / NK;
-  const bool tail = (f % NK) != 0;
+  const int64_t nk = (f + F64_K - 1) / F64_K;
+  const bool tail = (f % F64_K) != 0;
   // stage t landed (this wave's DMA) and visible to every wave; later stages may be in flight
   auto ready = [&](int64_t t) {
     const int64_t later = nk - 1 - t < AHEAD - 1 ? nk - 1 - t : AHEAD - 1;  // stages issued after t
     if (tail && t == nk - 1) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      ha_vm_wait<0>();
       zero_tail(t);
     }
-    if (later >= 2) kn64_wait_barrier<2 * NDPS>();
-    else if (later == 1) kn64_wait_barrier<NDPS>();
-    else kn64_wait_barrier<0>();
+    if (later >= 2) ha_wait_barrier<2 * F64_DPS>();
+    else if (later == 1) ha_wait_barrier<F64_DPS>();
+    else ha_wait_barrier<0>();
   };
   // steady state: stage t + AHEAD issued whole, the first half of the MFMAs around it, the counted
   // wait for stage t + 1 + barrier, the first part of stage t + 1's fragment reads between the second
@@ -282,7 +220,7 @@ __global__ __launch_bounds__(256, 2) void kn64_topk(const double* __restrict__ Q
     stage(t + AHEAD, true);
     mma_half(Fc, 0);
     __builtin_amdgcn_sched_barrier(0);
-    kn64_wait_barrier<(AHEAD - 1) * NDPS>();
+    ha_wait_barrier<(AHEAD - 1) * F64_DPS>();
     load(Fn, t + 1, 0);
     mma_half(Fc, 1);
     __builtin_amdgcn_sched_barrier(0);
@@ -494,7 +432,8 @@ HA_EXPORT int ha_knn_f64(const double* Q, int64_t nq, int64_t f, int64_t ldq, co
   const int64_t tiles = (nq + NT - 1) / NT, lim = 0x7fffffffLL - NT;
   if (nt >= lim || f >= lim || tiles > 0x7fffffffLL) return HA_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(kn64_norms, dim3((unsigned)((nt + 15) / 16)), dim3(256), 0, s, T, nt, ldt, f, ws);
+  hipLaunchKernelGGL(f64_row_norms, dim3((unsigned)((nt + 15) / 16)), dim3(256), 0, s, T, nt, ldt,
+                     (const double*)nullptr, (int64_t)0, (int64_t)0, f, ws);
   if (ha_launch_status() != HA_OK) return HA_LAUNCH;
   const dim3 grid((unsigned)tiles, (unsigned)splits);
   if (k <= 8)

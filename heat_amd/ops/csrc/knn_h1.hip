@@ -7,29 +7,13 @@
 namespace {
 
 // s_waitcnt vmcnt(N), expcnt / lgkmcnt left alone (gfx9 encoding: vmcnt bits 3:0 and 15:14,
-// expcnt 6:4, lgkmcnt 11:8)
+// expcnt 6:4, lgkmcnt 11:8). The builtin, not common.h's ha_vm_wait: the compiler's wait-count
+// pass accounts for a builtin wait, while behind the asm form it adds vmcnt terms of its own to
+// the waits in front of this kernel's MFMAs (8 - 36 changed instructions per h1_topk instance).
 template <int N>
 __device__ __forceinline__ void vm_wait() {
   static_assert(N >= 0 && N < 64, "vmcnt range");
   __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-
-// LDS-DMA of 16 bytes per lane (global_load_lds_dwordx4; LDS address = lds + 16 lane) issued
-// through inline asm: for the builtin the compiler's wait-count pass cannot tell which LDS bytes
-// the transfer writes and puts s_waitcnt vmcnt(0) before the next LDS read - i.e. it waits for
-// the prefetched chunks too. The asm form is invisible to that pass (its own vmcnt waits only
-// become more conservative); the kernel waits for its transfers with counted vm_wait<N>().
-// M0 (the LDS address of the transfer) is saved and restored around it: the compiler treats M0 as
-// reserved and would not see a clobber.
-// The LDS address is wave-uniform; readfirstlane pins it to an SGPR (inside a lane-divergent
-// branch the compiler may otherwise hand the "s" operand a VGPR).
-__device__ __forceinline__ void lds_dma16(const void* g, unsigned lds) {
-  unsigned saved;
-  const unsigned base = __builtin_amdgcn_readfirstlane(lds);
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(saved)
-               : "v"(g), "s"(base)
-               : "memory");
 }
 
 // Sorted insertion into a descending list with the eviction recorded in rej (the caller has
@@ -288,10 +272,10 @@ __global__ __launch_bounds__(64 * WAVES, MINB) void h1_topk(const _Float16* __re
 #pragma unroll
     for (int pc = tt; pc < IMGW; pc += TPI) {
       const int q = wave + WAVES * pc;
-      lds_dma16(gimg + ((int64_t)ch * PIECES + q) * 2048, dst + q * 1024);
+      ha_dma16(gimg + ((int64_t)ch * PIECES + q) * 2048, dst + q * 1024);
     }
     if (tt == 0 && vw && (2 * wave + 1 < TPI || lane < 32))
-      lds_dma16(gv + ((int64_t)ch * TPI + 2 * wave) * 512, dst + PIECES * 1024 + 2 * wave * 512);
+      ha_dma16(gv + ((int64_t)ch * TPI + 2 * wave) * 512, dst + PIECES * 1024 + 2 * wave * 512);
   };
   auto issue = [&](int ch) __attribute__((always_inline)) {
 #pragma unroll

@@ -343,15 +343,6 @@ __device__ __forceinline__ int vd_off(int kk, int col) {
   return ((kk & 3) + 4 * (kk >> 3)) * VD_PIECE + ((kk >> 2) & 1) * 512 + col * 4;
 }
 
-template <int N>
-__device__ __forceinline__ void vd_wait_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 __global__ __launch_bounds__(256, 2) void vtc64d(const float* __restrict__ V, int64_t ldv, const float* __restrict__ C,
                                                  int64_t ldc, int64_t m, int64_t nc, int64_t N, int64_t chunk,
                                                  double* __restrict__ P) {
@@ -393,9 +384,9 @@ __global__ __launch_bounds__(256, 2) void vtc64d(const float* __restrict__ V, in
   for (int t = 0; t < VD_NST - 1 && t < nst; ++t) issue(t);
   for (int t = 0; t < nst; ++t) {
     const int ahead = nst - 1 - t;  // stages issued after t (at most 2)
-    if (ahead >= 2) vd_wait_barrier<8>();
-    else if (ahead == 1) vd_wait_barrier<4>();
-    else vd_wait_barrier<0>();
+    if (ahead >= 2) ha_wait_barrier<8>();
+    else if (ahead == 1) ha_wait_barrier<4>();
+    else ha_wait_barrier<0>();
     unsigned char* b = smem + (t % VD_NST) * VD_STAGE;
     if (r0 + (int64_t)(t + 1) * VT_BK > r1) {
       // tail stage: zero this wave's k-rows past the chunk end (its own DMA has landed)
@@ -407,7 +398,7 @@ __global__ __launch_bounds__(256, 2) void vtc64d(const float* __restrict__ V, in
           *reinterpret_cast<floatx4*>(b + VD_OP + p * VD_PIECE + lane * 16) = (floatx4)(0.f);
         }
       }
-      vd_wait_barrier<0>();
+      ha_wait_barrier<0>();
     }
     if (t + VD_NST - 1 < nst) issue(t + VD_NST - 1);
 #pragma unroll
