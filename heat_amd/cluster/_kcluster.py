@@ -9,6 +9,7 @@ rows with ONE distributed take (the reference does k randint calls and k broadca
 """
 from __future__ import annotations
 
+import os
 from typing import Callable, Optional, Union
 
 import torch
@@ -228,13 +229,40 @@ def _keys_to_values(K: torch.Tensor, dtype) -> torch.Tensor:
     return k32.view(torch.float32)
 
 
+def kmedians_native(X: torch.Tensor) -> bool:
+    """Whether the k-medians / k-medoids hot path of ``X`` runs on ``csrc/kmedians.hip``: device
+    floating data unless ``HEAT_KMEDIANS_NATIVE=0`` (read at every call, for A/B runs)."""
+    return (os.environ.get("HEAT_KMEDIANS_NATIVE", "1") != "0" and X.dim() == 2
+            and X.dtype in (torch.float32, torch.float64) and ops.use_native(X))
+
+
+def l1_labels(x: DNDarray, centers: DNDarray) -> DNDarray:
+    """(n, 1) int64 labels of the nearest centre in the Manhattan metric (split like ``x``), ties to
+    the lowest centre: the fused ``ops.l1_assign`` for device data, else argmin of the cdist matrix."""
+    X = x.larray if x.larray.is_floating_point() else x.larray.float()
+    C = centers.larray.to(X.device)
+    if kmedians_native(X):
+        lab = ops.l1_assign(X, C, want_mind=False)[0]
+    else:
+        lab = torch.argmin(ops.cdist(X, C, "manhattan"), dim=1)
+    lab = lab.to(torch.int64).reshape(-1, 1)
+    return DNDarray(lab, (x.gshape[0], 1), ht.int64, x.split, x.device, x.comm, x.balanced)
+
+
+_MED_OPS = {"sum": MPI.SUM, "max": MPI.MAX}
+
+
 def cluster_medians(X: torch.Tensor, labels: torch.Tensor, k: int, comm, distributed: bool):
     """Exact per-(cluster, feature) medians of the rows of X grouped by ``labels``.
 
-    Bisection on the bit-ordered integer keys: every step counts, per (cluster, feature), the
-    members below the probe with one pass and ONE all-reduce of 2*k*f counts; <= 64 steps give
-    the exact lower/upper middle order statistics (averaged like NumPy's median).
-    Returns (medians [k, f], counts [k])."""
+    Device float data: the radix select of ``ops.cluster_medians`` (one packed all-reduce per digit
+    pass when split). Otherwise bisection on the bit-ordered integer keys: every step counts, per
+    (cluster, feature), the members below the probe with one pass and ONE all-reduce of 2*k*f
+    counts; <= 64 steps give the exact lower/upper middle order statistics (averaged like NumPy's
+    median). Returns (medians [k, f], counts [k])."""
+    if kmedians_native(X) and ops.kernels._med_native(X, k, distributed):
+        red = (lambda t, op: comm.Allreduce(MPI.IN_PLACE, t, _MED_OPS[op])) if distributed else None
+        return ops.cluster_medians(X, labels, k, red)
     n, f = X.shape
     lab = labels.reshape(-1).to(torch.int64)
     dev = X.device

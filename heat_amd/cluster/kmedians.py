@@ -13,7 +13,7 @@ import torch
 
 from .. import core as ht
 from ..core.dndarray import DNDarray
-from ._kcluster import _KCluster, cluster_medians
+from ._kcluster import _KCluster, cluster_medians, l1_labels
 
 
 class KMedians(_KCluster):
@@ -27,12 +27,7 @@ class KMedians(_KCluster):
                          init=init, max_iter=max_iter, tol=tol, random_state=random_state)
 
     def _assign_to_cluster(self, x: DNDarray) -> DNDarray:
-        from .. import ops
-
-        d = ops.cdist(x.larray.float() if not x.larray.is_floating_point() else x.larray,
-                      self._cluster_centers.larray.to(x.larray.device), "manhattan")
-        lab = torch.argmin(d, dim=1).to(torch.int64).reshape(-1, 1)
-        return DNDarray(lab, (x.gshape[0], 1), ht.int64, x.split, x.device, x.comm, x.balanced)
+        return l1_labels(x, self._cluster_centers)
 
     def _update_centroids(self, x: DNDarray, matching_centroids: DNDarray) -> DNDarray:
         X = x.larray if x.larray.is_floating_point() else x.larray.float()

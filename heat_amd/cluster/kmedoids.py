@@ -14,7 +14,8 @@ import torch
 from .. import core as ht
 from ..core.communication import MPI
 from ..core.dndarray import DNDarray
-from ._kcluster import _KCluster, cluster_medians
+from .. import ops
+from ._kcluster import _KCluster, cluster_medians, kmedians_native, l1_labels
 
 
 class KMedoids(_KCluster):
@@ -28,12 +29,7 @@ class KMedoids(_KCluster):
                          init=init, max_iter=max_iter, tol=0.0, random_state=random_state)
 
     def _assign_to_cluster(self, x: DNDarray) -> DNDarray:
-        from .. import ops
-
-        d = ops.cdist(x.larray.float() if not x.larray.is_floating_point() else x.larray,
-                      self._cluster_centers.larray.to(x.larray.device), "manhattan")
-        lab = torch.argmin(d, dim=1).to(torch.int64).reshape(-1, 1)
-        return DNDarray(lab, (x.gshape[0], 1), ht.int64, x.split, x.device, x.comm, x.balanced)
+        return l1_labels(x, self._cluster_centers)
 
     def _update_centroids(self, x: DNDarray, matching_centroids: DNDarray) -> DNDarray:
         k = self.n_clusters
@@ -41,7 +37,12 @@ class KMedoids(_KCluster):
         lab = matching_centroids.larray.reshape(-1).to(torch.int64)
         dist = x.is_distributed()
         med, cnt = cluster_medians(X, lab, k, x.comm, dist)
-        d = (X - med[lab]).abs().sum(1).double() if X.shape[0] else X.new_zeros(0, dtype=torch.float64)
+        if not X.shape[0]:
+            d = X.new_zeros(0, dtype=torch.float64)
+        elif kmedians_native(X):
+            d = ops.l1_to_label(X, med, lab).double()   # row kernel: no n x f difference tensor
+        else:
+            d = (X - med[lab]).abs().sum(1).double()
         inf = float("inf")
         best = torch.full((k,), inf, dtype=torch.float64, device=X.device)
         if X.shape[0]:

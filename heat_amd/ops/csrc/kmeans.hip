@@ -705,3 +705,49 @@ HA_EXPORT int ha_km_update_f64(const double* X, int64_t n, int f, int64_t ldx, c
                      sums, counts);
   return ha_launch_status();
 }
+
+// The counting-sort row order alone (k-medians' radix select walks it): the placement kernels of
+// the deterministic update, nothing else. int32 workspace layout: order [n] | block histograms |
+// totals [k] | cstart [k + 1] | fp32 counts [k]; ha_km_label_order_cstart is cstart's offset in it.
+// order holds the rows with a label in [0, k) by cluster, in row order inside a cluster;
+// cstart[c] .. cstart[c + 1] is cluster c's segment and cstart[k] the number of such rows.
+HA_EXPORT int64_t ha_km_label_order_workspace(int64_t n, int k) {
+  if (k <= 0 || n < 0 || (int64_t)k * 4 > 150 * 1024 || n >= (int64_t)1 << 31) return -1;
+  int64_t nblk, rows;
+  ku_grid(n, &nblk, &rows);
+  return n + nblk * k + k + (k + 1) + k;
+}
+
+HA_EXPORT int64_t ha_km_label_order_cstart(int64_t n, int k) {
+  if (ha_km_label_order_workspace(n, k) < 0) return -1;
+  int64_t nblk, rows;
+  ku_grid(n, &nblk, &rows);
+  return n + nblk * k + k;
+}
+
+HA_EXPORT int ha_km_label_order(const int* labels, int64_t n, int k, int* workspace, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n <= 0 || !labels || !workspace) return HA_BAD_ARG;
+  if (ha_km_label_order_workspace(n, k) < 0) return HA_UNSUPPORTED;
+  int64_t nblk, rows;
+  ku_grid(n, &nblk, &rows);
+  int* order = workspace;
+  int* hist = order + n;
+  int* total = hist + nblk * k;
+  int* cstart = total + k;
+  float* fcounts = reinterpret_cast<float*>(cstart + k + 1);
+  const size_t lds = (size_t)k * sizeof(int);
+  if (lds > 64 * 1024) hipFuncSetAttribute((const void*)ku_hist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(ku_hist, dim3((unsigned)nblk), dim3(KU_BLOCK), lds, s, labels, n, k, rows, hist,
+                     (float*)nullptr, (int64_t)0);
+  hipLaunchKernelGGL(ku_scan_blk, dim3((k + 255) / 256), dim3(256), 0, s, hist, (int)nblk, k, total);
+  hipLaunchKernelGGL(ku_scan_tot, dim3(1), dim3(1024), 0, s, total, k, cstart, fcounts);
+  int W = 16;  // waves per scatter block: their per-wave counts ([W][k] ints) must fit in LDS
+  while (W > 1 && (size_t)W * k * sizeof(int) > 128 * 1024) W >>= 1;
+  const size_t lds_det = (size_t)W * k * sizeof(int);
+  if (lds_det > 64 * 1024)
+    hipFuncSetAttribute((const void*)ku_scatter_det, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_det);
+  hipLaunchKernelGGL(ku_scatter_det, dim3((unsigned)nblk), dim3(64 * W), lds_det, s, labels, n, k, rows, W, hist,
+                     cstart, order);
+  return ha_launch_status();
+}

@@ -22,7 +22,8 @@ __all__ = ["kmeans_finalize", "pack_blocks", "unpack_blocks", "pack_supported", 
            "argreduce_decode", "argreduce_supported", "topk_rows", "gemm_f32", "gemm_h3", "h3_planes", "H3Planes",
            "gemm_h3_planes", "gemm64", "gemm_f64", "cholesky_upper", "tri_inv_upper", "householder_qr",
            "householder_factor", "householder_apply", "householder_block", "vtc64", "gram64",
-           "radix_sort_supported", "sort_rows", "class_moments", "gnb_jll", "GNB_MAX_CLASSES"]
+           "radix_sort_supported", "sort_rows", "class_moments", "gnb_jll", "GNB_MAX_CLASSES", "l1_assign",
+           "l1_to_label", "cluster_medians"]
 
 _NUM_CUS = {}
 
@@ -776,6 +777,7 @@ def moments4(x: torch.Tensor, axis: Optional[int] = None):
 
 # --------------------------------------------------------------------------------------------- naive Bayes
 GNB_MAX_CLASSES = 64   # what csrc/gnb.hip serves (4 class tiles of 16)
+MED_MAX_TABLE_BYTES = 256 << 20   # cluster_medians: cap of the [k, f, 256] u32 digit table (k * f * 1 KB)
 
 
 def _gnb_native(X: torch.Tensor, k: int) -> bool:
@@ -864,6 +866,151 @@ def gnb_jll(X: torch.Tensor, theta: torch.Tensor, sigma: torch.Tensor, log_prior
     if mode == 1:
         return torch.argmax(jll, dim=1)
     return jll - torch.logsumexp(jll, dim=1, keepdim=True) if mode == 2 else jll
+
+
+# --------------------------------------------------------------------------------------------- k-medians
+def _l1_native(X: torch.Tensor) -> bool:
+    return X.dim() == 2 and use_native(X) and X.dtype in (torch.float32, torch.float64)
+
+
+def _l1_rows(X: torch.Tensor) -> torch.Tensor:
+    """X as csrc/kmedians.hip reads it: unit feature stride, element-aligned, any row stride >= f."""
+    ok = X.stride(1) == 1 and X.data_ptr() % X.element_size() == 0 and (X.shape[0] == 1 or X.stride(0) >= X.shape[1])
+    return X if ok else X.contiguous()
+
+
+def l1_assign(X: torch.Tensor, C: torch.Tensor, want_mind: bool = True):
+    """(labels int32 [n], mind [n] | None): the first-index argmin over the rows of ``C`` [k, f] of the
+    Manhattan distance ``sum_j |X[i, j] - C[c, j]|`` and that minimum, the features summed in index
+    order in ``X``'s precision.
+
+    Device float32 / float64 ``X``: one fused kernel (``csrc/kmedians.hip``), no n x k matrix. Host
+    tensors: argmin of the ``cdist`` matrix."""
+    if X.dim() != 2 or C.dim() != 2 or C.shape[0] < 1 or C.shape[1] != X.shape[1] or X.shape[1] < 1:
+        raise ValueError("l1_assign: X [n, f] and C [k, f] with k, f >= 1")
+    if not _l1_native(X):
+        d = cdist(X, C.to(device=X.device, dtype=X.dtype), "manhattan")
+        lab = torch.argmin(d, dim=1)
+        return lab.to(torch.int32), (d.gather(1, lab.unsqueeze(1)).squeeze(1) if want_mind else None)
+    n, f = X.shape
+    Xc, Cc = _l1_rows(X), _l1_rows(C.to(device=X.device, dtype=X.dtype))
+    k = Cc.shape[0]
+    labels = torch.empty(n, dtype=torch.int32, device=X.device)
+    mind = torch.empty(n, dtype=X.dtype, device=X.device) if want_mind else None
+    check(lib().ha_l1_assign(_ptr(Xc), 0 if X.dtype == torch.float32 else 1, n, f, Xc.stride(0) if n > 1 else f,
+                             _ptr(Cc), k, Cc.stride(0) if k > 1 else f, _ptr(labels), _ptr(mind),
+                             ctypes.c_void_p(stream_ptr(X.device))), "ha_l1_assign")
+    return labels, mind
+
+
+def l1_to_label(X: torch.Tensor, M: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """d [n] in ``X``'s type, ``d[i] = sum_j |X[i, j] - M[labels[i], j]|`` (device float32 / float64: one
+    row kernel of ``csrc/kmedians.hip``, no n x f difference tensor)."""
+    if X.dim() != 2 or M.dim() != 2 or M.shape[1] != X.shape[1] or labels.numel() != X.shape[0]:
+        raise ValueError("l1_to_label: X [n, f], M [k, f] and one label per row")
+    if not _l1_native(X) or X.shape[1] < 1 or M.shape[0] < 1:
+        return (X - M.to(device=X.device, dtype=X.dtype)[labels.reshape(-1).to(torch.int64)]).abs().sum(1)
+    n, f = X.shape
+    Xc, Mc = _l1_rows(X), _l1_rows(M.to(device=X.device, dtype=X.dtype))
+    k = Mc.shape[0]
+    lab = labels.reshape(-1).to(device=X.device, dtype=torch.int32).contiguous()
+    d = torch.empty(n, dtype=X.dtype, device=X.device)
+    check(lib().ha_l1_to_label(_ptr(Xc), 0 if X.dtype == torch.float32 else 1, n, f, Xc.stride(0) if n > 1 else f,
+                               _ptr(Mc), k, Mc.stride(0) if k > 1 else f, _ptr(lab), _ptr(d),
+                               ctypes.c_void_p(stream_ptr(X.device))), "ha_l1_to_label")
+    return d
+
+
+# Pass-count policy of cluster_medians: one host read of the largest digit count per call (default)
+# against always running the worst case (4 / 8 passes, exhausted entries idle, no host read). Measured
+# at 4e6 x 64 (profiles/kmedians.jsonl, legs native / native_fixed): the same within noise on k blobs
+# (KMedians float32 k = 8 2.42 vs 2.38 ms, float64 k = 128 9.12 vs 8.98 ms), so the host read stays - it
+# also skips the launches of the idle passes and the call already ends in host-visible results. Kept as
+# a switch for tools/microbench/kmedians.py. The digit width stays 8 bits (a [64][256] u32 histogram is
+# 64 KB of LDS, two workgroups per CU); wider digits were not measured.
+_MED_FIXED_PASSES = os.environ.get("HEAT_MED_FIXED_PASSES", "0") == "1"
+
+
+def _med_native(X: torch.Tensor, k: int, empty_ok: bool = False) -> bool:
+    """Whether :func:`cluster_medians` serves ``X``: device float32 / float64 matrix with rows (a rank
+    of a split array may have none: ``empty_ok``), and the [k, f, 256] digit table within
+    MED_MAX_TABLE_BYTES."""
+    return (_l1_native(X) and (X.shape[0] > 0 or empty_ok) and X.shape[1] > 0
+            and lib().ha_med_table_bytes(k, X.shape[1], MED_MAX_TABLE_BYTES) >= 0
+            and lib().ha_km_label_order_workspace(X.shape[0], k) >= 0)
+
+
+def cluster_medians(X: torch.Tensor, labels: torch.Tensor, k: int, allreduce=None):
+    """Exact medians (med [k, f] in ``X``'s type, counts float64 [k]) of the rows of the device matrix
+    ``X`` grouped by ``labels``: the mean, in float64, of the lower and upper middle order statistics of
+    every (cluster, feature), as NumPy's median; 0 for a cluster without rows. Labels outside [0, k)
+    are ignored.
+
+    MSD radix select (``csrc/kmedians.hip``) over the counting-sort row order of ``csrc/kmeans.hip``:
+    one pass for the per-entry key minimum and maximum, one 8-bit histogram pass per digit in which an
+    entry's keys differ (at most 4 for float32, 8 for float64; the number is read from the device once
+    per call), one fix-up pass for the upper statistic. ``X`` is read in place - no key copy, no n x f
+    temporary.
+
+    ``allreduce(t, op)`` reduces the device tensor ``t`` in place over the ranks, ``op`` being "sum" or
+    "max": called on the counts and the min/max table after pass 0, on the [k, f, 256] int32 digit
+    table of every select pass, and on the two fix-up tables (minima travel as maxima of ~key)."""
+    if X.dim() != 2 or k <= 0:
+        raise ValueError("cluster_medians: X must be a matrix and k positive")
+    if not _med_native(X, k, allreduce is not None):
+        raise ValueError("cluster_medians needs a device float32 / float64 matrix with rows and k * f * 1 KB <= "
+                         "{} bytes".format(MED_MAX_TABLE_BYTES))
+    if X.shape[0] == 0:
+        # a rank without rows still takes part in every reduction: one row that no cluster owns
+        X, labels = X.new_zeros((1, X.shape[1])), torch.full((1,), -1, dtype=torch.int32, device=X.device)
+    L = lib()
+    n, f = X.shape
+    dev = X.device
+    st = ctypes.c_void_p(stream_ptr(dev))
+    dt, kt = (0, torch.int32) if X.dtype == torch.float32 else (1, torch.int64)
+    Xc = _l1_rows(X)
+    ldx = Xc.stride(0) if n > 1 else f
+    lab = labels.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    if lab.numel() != n:
+        raise ValueError("cluster_medians: one label per row of X")
+    ws = torch.empty(L.ha_km_label_order_workspace(n, k), dtype=torch.int32, device=dev)
+    check(L.ha_km_label_order(_ptr(lab), n, k, _ptr(ws), st), "ha_km_label_order")
+    order, cstart = ws, ws[L.ha_km_label_order_cstart(n, k):]
+    counts = (cstart[1:k + 1] - cstart[:k]).to(torch.int64)
+    smallest = torch.iinfo(kt).min
+    mm = torch.full((2, k, f), smallest, dtype=kt, device=dev)
+    check(L.ha_med_minmax(_ptr(Xc), dt, n, f, ldx, _ptr(order), _ptr(cstart), k, _ptr(mm), st), "ha_med_minmax")
+    if allreduce is not None:
+        allreduce(counts, "sum")
+        allreduce(mm, "max")
+    prefix = torch.empty((k, f), dtype=kt, device=dev)
+    rank = torch.empty((k, f), dtype=torch.int64, device=dev)
+    npass = torch.empty((k, f), dtype=torch.int32, device=dev)
+    maxpass = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(L.ha_med_setup(dt, _ptr(mm), _ptr(counts), k, f, _ptr(prefix), _ptr(rank), _ptr(npass), _ptr(maxpass), st),
+          "ha_med_setup")
+    passes = (4 if dt == 0 else 8) if _MED_FIXED_PASSES else int(maxpass.item())
+    if passes:
+        table = torch.zeros((k, f, 256), dtype=torch.int32, device=dev)
+        tbytes = table.numel() * 4
+        for p in range(passes):
+            check(L.ha_med_select(_ptr(Xc), dt, n, f, ldx, _ptr(order), _ptr(cstart), k, _ptr(mm), _ptr(prefix),
+                                  _ptr(npass), p, _ptr(table), tbytes, st), "ha_med_select")
+            if allreduce is not None:
+                allreduce(table, "sum")
+            check(L.ha_med_pick(dt, k, f, p, _ptr(table), tbytes, _ptr(prefix), _ptr(rank), _ptr(npass), st),
+                  "ha_med_pick")
+        del table
+    fx = torch.zeros((2, k, f), dtype=kt, device=dev)
+    fx[0].fill_(smallest)
+    check(L.ha_med_fixup(_ptr(Xc), dt, n, f, ldx, _ptr(order), _ptr(cstart), k, _ptr(mm), _ptr(prefix), _ptr(fx), st),
+          "ha_med_fixup")
+    if allreduce is not None:
+        allreduce(fx[0], "max")
+        allreduce(fx[1], "sum")
+    med = torch.empty((k, f), dtype=X.dtype, device=dev)
+    check(L.ha_med_finish(dt, k, f, _ptr(mm), _ptr(prefix), _ptr(counts), _ptr(fx), _ptr(med), st), "ha_med_finish")
+    return med, counts.to(torch.float64)
 
 
 # --------------------------------------------------------------------------------------------- cdist

@@ -44,6 +44,30 @@ int ha_threefry_fill(void* out, int64_t e0, int64_t n, uint64_t counter_lo, uint
                      int bits, int dist, double low, double span, void* stream);
 int ha_knn_rescore(const float* Q, int64_t ldq, const float* T, int64_t ldt, int64_t nt, int64_t nq, int f,
                    const void* cand, int idx64, int c, int k, float* dist, int64_t* out_idx, void* stream);
+int64_t ha_km_label_order_workspace(int64_t n, int k);
+int64_t ha_km_label_order_cstart(int64_t n, int k);
+int ha_km_label_order(const int* labels, int64_t n, int k, int* workspace, void* stream);
+int ha_l1_point_block();
+int ha_l1_centroid_tile(int k);
+int ha_l1_assign(const void* X, int dtype, int64_t n, int f, int64_t ldx, const void* C, int k, int64_t ldc, int* labels,
+                 void* mind, void* stream);
+int ha_l1_to_label(const void* X, int dtype, int64_t n, int f, int64_t ldx, const void* M, int k, int64_t ldm,
+                   const int* labels, void* d, void* stream);
+int ha_med_segment();
+int64_t ha_med_table_bytes(int k, int f, int64_t cap);
+int ha_med_minmax(const void* X, int dtype, int64_t n, int f, int64_t ldx, const int* order, const int* cstart, int k,
+                  void* mm, void* stream);
+int ha_med_setup(int dtype, const void* mm, const void* counts, int k, int f, void* prefix, void* rank, int* npass,
+                 int* maxpass, void* stream);
+int ha_med_select(const void* X, int dtype, int64_t n, int f, int64_t ldx, const int* order, const int* cstart, int k,
+                  const void* mm, const void* prefix, const int* npass, int pass, void* table, int64_t table_bytes,
+                  void* stream);
+int ha_med_pick(int dtype, int k, int f, int pass, void* table, int64_t table_bytes, void* prefix, void* rank,
+                const int* npass, void* stream);
+int ha_med_fixup(const void* X, int dtype, int64_t n, int f, int64_t ldx, const int* order, const int* cstart, int k,
+                 const void* mm, const void* prefix, void* fx, void* stream);
+int ha_med_finish(int dtype, int k, int f, const void* mm, const void* prefix, const void* counts, const void* fx,
+                  void* med, void* stream);
 }
 
 static int fails = 0;
@@ -117,6 +141,53 @@ int main() {
   CHECK(ha_knn_rescore(nullptr, 4, nullptr, 4, 10, 5, 4, nullptr, 0, 16, 17, nullptr, nullptr, nullptr) == BAD);  // k > c
   CHECK(ha_knn_rescore(nullptr, 2, nullptr, 4, 10, 5, 4, nullptr, 0, 16, 8, nullptr, nullptr, nullptr) == BAD);  // ldq < f
   CHECK(ha_knn_rescore(nullptr, 4, nullptr, 4, 10, 0, 4, nullptr, 0, 16, 8, nullptr, nullptr, nullptr) == OK);   // nq = 0
+  // k-medians: the label order's workspace, the digit table's capacity, the wrappers' rejections
+  const int64_t cap = (int64_t)256 << 20;
+  for (int64_t n : sizes)
+    for (int k : {1, 7, 128, 4096}) {
+      const int64_t w = ha_km_label_order_workspace(n, k), c = ha_km_label_order_cstart(n, k);
+      CHECK(w >= n + 3 * (int64_t)k + 1 && c >= n && c + k + 1 <= w);
+      for (int f : {1, 3, 64, 65}) {
+        const int64_t b = ha_med_table_bytes(k, f, cap);
+        CHECK(b == ((int64_t)k * f * 1024 <= cap ? (int64_t)k * f * 1024 : -1));
+      }
+    }
+  CHECK(ha_km_label_order_workspace(10, 0) == -1 && ha_km_label_order_workspace((int64_t)1 << 31, 4) == -1);
+  CHECK(ha_med_table_bytes(0, 4, cap) == -1 && ha_med_table_bytes(4, 0, cap) == -1);
+  CHECK(ha_med_table_bytes(4096, 65, cap) == -1);  // cap exceeded
+  CHECK(ha_l1_point_block() > 0 && ha_med_segment() > 0);
+  for (int k : {1, 16, 17, 1000}) CHECK(ha_l1_centroid_tile(k) % 16 == 0);
+  int idummy[16] = {0};
+  CHECK(ha_km_label_order(nullptr, 4, 2, idummy, nullptr) == BAD);
+  CHECK(ha_km_label_order(idummy, 4, 2, nullptr, nullptr) == BAD);
+  CHECK(ha_km_label_order(idummy, 4, 0, idummy, nullptr) == UNSUP);
+  CHECK(ha_l1_assign(nullptr, 0, 4, 4, 4, dummy, 2, 4, idummy, nullptr, nullptr) == BAD);
+  CHECK(ha_l1_assign(dummy, 0, 4, 4, 4, nullptr, 2, 4, idummy, nullptr, nullptr) == BAD);
+  CHECK(ha_l1_assign(dummy, 0, 4, 4, 4, dummy, 2, 4, nullptr, nullptr, nullptr) == BAD);
+  CHECK(ha_l1_assign(dummy, 0, 4, 4, 4, dummy, 0, 4, idummy, nullptr, nullptr) == BAD);   // k <= 0
+  CHECK(ha_l1_assign(dummy, 0, 4, 0, 4, dummy, 2, 4, idummy, nullptr, nullptr) == BAD);   // f <= 0
+  CHECK(ha_l1_assign(dummy, 0, 4, 4, 2, dummy, 2, 4, idummy, nullptr, nullptr) == BAD);   // ldx < f
+  CHECK(ha_l1_assign(dummy, 2, 4, 4, 4, dummy, 2, 4, idummy, nullptr, nullptr) == BAD);   // dtype
+  CHECK(ha_l1_assign(dummy, 0, 0, 4, 4, dummy, 2, 4, idummy, nullptr, nullptr) == OK);    // n = 0
+  CHECK(ha_l1_to_label(dummy, 0, 4, 4, 4, dummy, 2, 4, nullptr, dummy, nullptr) == BAD);
+  CHECK(ha_l1_to_label(dummy, 0, 4, 4, 4, dummy, -1, 4, idummy, dummy, nullptr) == BAD);  // k <= 0
+  CHECK(ha_l1_to_label(dummy, 1, 4, -3, 4, dummy, 2, 4, idummy, dummy, nullptr) == BAD);  // f <= 0
+  CHECK(ha_med_minmax(nullptr, 0, 4, 4, 4, idummy, idummy, 2, dummy, nullptr) == BAD);
+  CHECK(ha_med_minmax(dummy, 0, 4, 4, 4, idummy, idummy, 0, dummy, nullptr) == BAD);      // k <= 0
+  CHECK(ha_med_minmax(dummy, 0, 4, 0, 4, idummy, idummy, 2, dummy, nullptr) == BAD);      // f <= 0
+  CHECK(ha_med_setup(0, dummy, dummy, 2, 4, dummy, nullptr, idummy, idummy, nullptr) == BAD);
+  CHECK(ha_med_setup(0, dummy, dummy, 0, 4, dummy, dummy, idummy, idummy, nullptr) == BAD);
+  CHECK(ha_med_select(dummy, 0, 4, 4, 4, idummy, idummy, 2, dummy, dummy, idummy, 0, nullptr, 8192, nullptr) == BAD);
+  CHECK(ha_med_select(dummy, 0, 4, 4, 4, idummy, idummy, 2, dummy, dummy, idummy, 4, dummy, 8192, nullptr) == BAD);
+  CHECK(ha_med_select(dummy, 0, 4, 4, 4, idummy, idummy, 2, dummy, dummy, idummy, 0, dummy, 8191, nullptr) ==
+        UNSUP);  // table smaller than k f 1 KB
+  CHECK(ha_med_pick(0, 2, 4, 0, dummy, 8191, dummy, dummy, idummy, nullptr) == UNSUP);
+  CHECK(ha_med_pick(0, 2, 4, 0, nullptr, 8192, dummy, dummy, idummy, nullptr) == BAD);
+  CHECK(ha_med_pick(1, 2, 0, 0, dummy, 8192, dummy, dummy, idummy, nullptr) == BAD);      // f <= 0
+  CHECK(ha_med_fixup(dummy, 0, 4, 4, 4, idummy, idummy, 2, dummy, dummy, nullptr, nullptr) == BAD);
+  CHECK(ha_med_fixup(dummy, 0, 4, 4, 4, idummy, idummy, -2, dummy, dummy, dummy, nullptr) == BAD);
+  CHECK(ha_med_finish(0, 2, 4, dummy, dummy, dummy, dummy, nullptr, nullptr) == BAD);
+  CHECK(ha_med_finish(0, 0, 4, dummy, dummy, dummy, dummy, dummy, nullptr) == BAD);       // k <= 0
   if (fails) {
     fprintf(stderr, "%d checks failed\n", fails);
     return 1;
