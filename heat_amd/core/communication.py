@@ -770,6 +770,7 @@ class MPICommunication(Communication):
         if self.size == 1:
             blk = send_blocks[0].reshape(recv_shapes[0])
             return None, lambda: [blk]
+        PATH_COUNTS["alltoallv:exchange"] += 1
         ref = next((b for b in send_blocks if b is not None), None)
         dtype, device = ref.dtype, ref.device
         wire = _WIRE.get(dtype, dtype)
@@ -806,6 +807,7 @@ class MPICommunication(Communication):
         if self.size == 1:
             out = send.reshape(recv_shape) if tuple(send.shape) == recv_shape else send
             return None, lambda: out
+        PATH_COUNTS["alltoallv:axis"] += 1
         packed = _k.pack_blocks(send, send_axis, scounts)
         in_b, out_b = exchange_axis_bytes(tuple(send.shape), send_axis, scounts, recv_shape, recv_axis, rcounts,
                                           send.element_size())

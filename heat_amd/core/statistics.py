@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _operations, factories, types
-from .communication import MPI
+from .communication import MPI, PATH_COUNTS
 from .dndarray import DNDarray
 from .stride_tricks import sanitize_axis
 from .. import ops
@@ -592,7 +592,9 @@ def _interp(lo_v, hi_v, frac, interpolation):
 
 def percentile(x: DNDarray, q, axis: Optional[int] = None, out: Optional[DNDarray] = None,
                interpolation: str = "linear", keepdim: bool = False) -> DNDarray:
-    """q-th percentile(s) along ``axis`` (distributed sort along the split axis)."""
+    """q-th percentile(s) along ``axis``. Device float32 / float64 data: exact radix select
+    (:func:`heat_amd.ops.order_statistics`), also along the split axis. Otherwise ``torch.quantile``, and a
+    distributed sort along the split axis."""
     from .manipulations import flatten, sort
 
     if not isinstance(x, DNDarray):
@@ -624,22 +626,31 @@ def percentile(x: DNDarray, q, axis: Optional[int] = None, out: Optional[DNDarra
     n = src.gshape[ax]
     rdtype = _result_dtype(x)
     tdt = torch.float64 if rdtype is types.float64 else torch.float32
-    if src.is_distributed() and ax == src.split:
-        vals, _ = sort(src, axis=ax)
+    along_split = src.is_distributed() and ax == src.split
+    native = n > 0 and ops.kernels._qsel_native(src.larray, along_split)
+    if along_split or native:
         positions = []
         for v in qv:
             pos = v / 100.0 * (n - 1)
             positions.append((int(np.floor(pos)), int(np.ceil(pos)), pos - np.floor(pos)))
         need = sorted(set([p for lo, hi, _ in positions for p in (lo, hi)]))
-        idx = torch.tensor(need, dtype=torch.int64)
-        key = [slice(None)] * vals.ndim
-        key[ax] = idx
-        picked = vals[tuple(key)]._gathered()
+        if native:
+            # radix select (ops.order_statistics): no sort; along the split axis one small integer
+            # all-reduce per digit pass and every rank holds the replicated result
+            red = (lambda t, op: src.comm.Allreduce(MPI.IN_PLACE, t, MPI.SUM)) if along_split else None
+            picked = ops.order_statistics(src.larray, need, axis=ax, allreduce=red, n_total=n)
+            PATH_COUNTS["percentile:native"] += 1
+        else:
+            vals, _ = sort(src, axis=ax)
+            idx = torch.tensor(need, dtype=torch.int64)
+            key = [slice(None)] * vals.ndim
+            key[ax] = idx
+            picked = vals[tuple(key)]._gathered().movedim(ax, 0)
         where = {p: i for i, p in enumerate(need)}
         res = []
         for lo, hi, frac in positions:
-            lo_v = picked.narrow(ax, where[lo], 1).squeeze(ax).to(tdt)
-            hi_v = picked.narrow(ax, where[hi], 1).squeeze(ax).to(tdt)
+            lo_v = picked[where[lo]].to(tdt)
+            hi_v = picked[where[hi]].to(tdt)
             if interpolation == "nearest":
                 # NumPy rounds a half position to the even index
                 res.append(hi_v if frac > 0.5 or (frac == 0.5 and hi % 2 == 0) else lo_v)
@@ -647,11 +658,19 @@ def percentile(x: DNDarray, q, axis: Optional[int] = None, out: Optional[DNDarra
             res.append(_interp(lo_v, hi_v, torch.tensor(frac, dtype=tdt, device=lo_v.device), interpolation))
         r = torch.stack(res)
         split = None
+        if not along_split and src.split is not None and src.is_distributed():
+            split = (src.split if src.split < ax else src.split - 1) + 1
     else:
         t = src.larray.to(tdt)
+        if t.is_cuda and src.larray.dtype == torch.float32 and interpolation == "linear":
+            # device float32 data with the kernels switched off (HEAT_QUANTILE_NATIVE=0): torch.quantile
+            # forms the position q * (n - 1) in the data's type, and a float32 position moves the
+            # interpolation weight by ~n * 2^-24 (9.7x the 4 eps bound of the kernel path at n = 4097).
+            # The same call on a float64 copy, rounded once at the end, keeps that path inside the bound.
+            t = t.double()
         # q / 100 on the host: a device division by a scalar is a multiply by its reciprocal, which
         # moves e.g. 95 / 100 one ulp up and flips "nearest" at a half position (28.5 -> 29 for n = 31)
-        qt = torch.tensor([v / 100.0 for v in qv], dtype=tdt, device=t.device)
+        qt = torch.tensor([v / 100.0 for v in qv], dtype=t.dtype, device=t.device)
         r = torch.quantile(t, qt, dim=ax, interpolation=interpolation) if t.numel() else \
             torch.empty((len(qv),) + tuple(s for i, s in enumerate(t.shape) if i != ax), dtype=tdt, device=t.device)
         split = None

@@ -7,47 +7,9 @@
 //                   ~100 bisection passes with n x f 8-byte temporaries by <= 4 (fp32) / 8 (fp64)
 //                   histogram passes plus one min/max and one fix-up pass.
 // There is no MFMA form of L1: everything here is VALU + LDS.
-#include "common.h"
+#include "radix_key.h"
 
 namespace {
-
-typedef double med_doublex2 __attribute__((ext_vector_type(2)));
-
-template <typename T> struct Tr;
-template <> struct Tr<float> {
-  typedef floatx4 vec;
-  typedef int S;        // bit-ordered key
-  typedef unsigned U;   // key distance
-  static constexpr int V = 4, BITS = 32;
-};
-template <> struct Tr<double> {
-  typedef med_doublex2 vec;
-  typedef long long S;
-  typedef unsigned long long U;
-  static constexpr int V = 2, BITS = 64;
-};
-
-// 16 bytes of a row starting at feature col (zeros past f and past the last row): one 16-byte
-// non-temporal load where the row is 16-byte aligned and the vector lies inside it, element loads
-// otherwise (odd f, unaligned views; a row is never read past its f features).
-template <typename T>
-__device__ __forceinline__ typename Tr<T>::vec ld_row(const T* __restrict__ base, int64_t row, int64_t nrows,
-                                                      int64_t ld, int col, int f, int vec_ok) {
-  typedef typename Tr<T>::vec vec;
-  constexpr int V = Tr<T>::V;
-  vec v = (vec)((T)0);
-  if (row < nrows && col < f) {
-    const T* p = base + row * ld + col;
-    if (vec_ok && col + V <= f) {
-      v = __builtin_nontemporal_load(reinterpret_cast<const vec*>(p));
-    } else {
-#pragma unroll
-      for (int q = 0; q < V; ++q)
-        if (col + q < f) v[q] = p[q];
-    }
-  }
-  return v;
-}
 
 // ------------------------------------------------------------------------------ fused L1 assignment
 // A workgroup of 256 threads owns L1_PB = 128 points. Threads form a 16 x 16 grid: thread (tr, tc)
@@ -196,21 +158,8 @@ __global__ __launch_bounds__(256) void l1_row_k(const T* __restrict__ X, int64_t
 }
 
 // ----------------------------------------------------------------------------------- exact medians
-// Keys: the monotone bit map of cluster/_kcluster.py (x < y <=> key(x) < key(y) as signed integers;
-// +-0 and NaN patterns order by their bits). All tables hold signed keys so that the caller's MAX
+// Keys: key_of / value_of of radix_key.h. All tables hold signed keys so that the caller's MAX
 // reduction orders them; a minimum travels as the maximum of the complement (~s = -1 - s).
-template <typename T>
-__device__ __forceinline__ typename Tr<T>::S key_of(T x) {
-  typedef typename Tr<T>::S S;
-  const S i = __builtin_bit_cast(S, x);
-  return i ^ ((i >> (Tr<T>::BITS - 1)) & ~((S)1 << (Tr<T>::BITS - 1)));
-}
-template <typename T>
-__device__ __forceinline__ T value_of(typename Tr<T>::S s) {
-  typedef typename Tr<T>::S S;
-  return __builtin_bit_cast(T, (S)(s ^ ((s >> (Tr<T>::BITS - 1)) & ~((S)1 << (Tr<T>::BITS - 1)))));
-}
-
 constexpr int MED_SEG = 4096;  // sorted positions per workgroup
 constexpr int MED_FT = 64;     // features per workgroup tile
 constexpr int MED_HS = 257;    // histogram row stride (256 would put a digit of every feature on one bank)

@@ -23,7 +23,7 @@ __all__ = ["kmeans_finalize", "pack_blocks", "unpack_blocks", "pack_supported", 
            "gemm_h3_planes", "gemm64", "gemm_f64", "cholesky_upper", "tri_inv_upper", "householder_qr",
            "householder_factor", "householder_apply", "householder_block", "vtc64", "gram64",
            "radix_sort_supported", "sort_rows", "class_moments", "gnb_jll", "GNB_MAX_CLASSES", "l1_assign",
-           "l1_to_label", "cluster_medians"]
+           "l1_to_label", "cluster_medians", "order_statistics"]
 
 _NUM_CUS = {}
 
@@ -1011,6 +1011,165 @@ def cluster_medians(X: torch.Tensor, labels: torch.Tensor, k: int, allreduce=Non
     med = torch.empty((k, f), dtype=X.dtype, device=dev)
     check(L.ha_med_finish(dt, k, f, _ptr(mm), _ptr(prefix), _ptr(counts), _ptr(fx), _ptr(med), st), "ha_med_finish")
     return med, counts.to(torch.float64)
+
+
+# --------------------------------------------------------------------------------------------- quantiles
+QSEL_MAX_TABLE_BYTES = 256 << 20   # order_statistics: cap of a pass's int64 table; more slices run in blocks
+# order_statistics compacts the keys under the targets' prefixes when they are at most 1 / this of the
+# slice (csrc/quantile.hip); the intended quarter, kept as it is - other values were not measured
+QSEL_COMPACT_DIV = 4
+
+
+def _qsel_native(x: torch.Tensor, distributed: bool = False) -> bool:
+    """Whether :func:`order_statistics` runs ``x`` on the radix-select kernels: device float32 / float64
+    with elements (a rank of a split array may have none: ``distributed``), unless
+    ``HEAT_QUANTILE_NATIVE=0`` (read at every call)."""
+    return (os.environ.get("HEAT_QUANTILE_NATIVE", "1") != "0" and x.dtype in (torch.float32, torch.float64)
+            and use_native(x) and (x.numel() > 0 or distributed))
+
+
+def _qsel_block(ptr: int, x: torch.Tensor, layout: int, sb: int, n: int, ld: int, ranks, allreduce, n_total: int):
+    """The radix select of ``sb`` slices starting at the device address ``ptr`` (rows: slice s at
+    ``ptr + s * ld`` elements; cols: column s of a matrix with row stride ``ld``): out [R, sb]."""
+    L = lib()
+    dev, R = x.device, len(ranks)
+    st = ctypes.c_void_p(stream_ptr(dev))
+    dt = 0 if x.dtype == torch.float32 else 1
+    npass, G, ncu = L.ha_qsel_passes(dt, layout), L.ha_qsel_group(), num_cus(dev)
+    cap = QSEL_MAX_TABLE_BYTES // 8
+    src = ctypes.c_void_p(ptr)
+    state = torch.zeros((4, sb, R), dtype=torch.int64, device=dev)
+    prefix, rank, cnt, key = state.unbind(0)
+    live = torch.zeros((sb, R), dtype=torch.int32, device=dev)
+    nan = torch.zeros(sb + 1, dtype=torch.int64, device=dev)
+    record = nan[sb:]
+    ranks_t = torch.tensor(ranks, dtype=torch.int64, device=dev)
+    comp = ccnt = None
+    ccap = 0
+
+    def row_chunks(length):
+        # 8 workgroups per CU over all slices, 8K elements at least each; a chunk holds at most 2^30
+        return max(1, min(65535, (8 * ncu + sb - 1) // sb, (length + 8191) // 8192), (length + 2 ** 30 - 1) // 2 ** 30)
+
+    def run(p, t0, tg, table):
+        append = 1 if (comp is not None and p == 1 and t0 == 0) else 0
+        if comp is not None and p >= 2:
+            check(L.ha_qsel_rows_pass(None, dt, layout, 1, sb, ccap, ccap, row_chunks(ccap), p, R, t0, tg, 0,
+                                      _ptr(prefix), _ptr(live), _ptr(table), table.numel(), _ptr(comp), _ptr(ccnt),
+                                      ccap, st), "ha_qsel_rows_pass")
+        elif layout == 0:
+            check(L.ha_qsel_rows_pass(src, dt, 0, 0, sb, n, ld, row_chunks(n), p, R, t0, tg, append, _ptr(prefix),
+                                      _ptr(live), _ptr(table), table.numel(), _ptr(comp), _ptr(ccnt), ccap, st),
+                  "ha_qsel_rows_pass")
+        else:
+            tiles = (sb + 15) // 16
+            nchunks = max(1, min(65535, (8 * ncu + tiles - 1) // tiles, (n + 255) // 256))
+            check(L.ha_qsel_cols_pass(src, dt, n, sb, ld, nchunks, p, R, t0, tg, append, _ptr(prefix), _ptr(live),
+                                      _ptr(table), table.numel(), _ptr(comp), _ptr(ccnt), ccap, st),
+                  "ha_qsel_cols_pass")
+
+    def pick(p, table):
+        if allreduce is not None:
+            allreduce(table, "sum")
+        check(L.ha_qsel_pick(dt, layout, sb, R, p, _ptr(ranks_t), _ptr(table), table.numel(), _ptr(prefix), _ptr(rank),
+                             _ptr(cnt), _ptr(live), _ptr(key), _ptr(nan), _ptr(record), st), "ha_qsel_pick")
+
+    te = [L.ha_qsel_table_elems(layout, sb, R, p, cap) for p in (0, 1)]
+    if min(te) < 0:
+        raise RuntimeError("order_statistics: {} slices x {} ranks are beyond the digit table".format(sb, R))
+    table = torch.zeros(te[0], dtype=torch.int64, device=dev)
+    if n > 0:
+        run(0, 0, 1, table)
+    pick(0, table)
+    matched = int(record.item())   # the one device read of the call
+    if npass > 2 and 0 < matched <= n_total // QSEL_COMPACT_DIV:
+        ccap = max(1, min(matched, n))
+        comp = torch.empty(sb * ccap, dtype=x.dtype, device=dev)
+        ccnt = torch.zeros(sb, dtype=torch.int64, device=dev)
+    table = torch.empty(te[1], dtype=torch.int64, device=dev)
+    for p in range(1, npass):
+        table.zero_()
+        if n > 0:
+            for t0 in range(0, R, G):
+                run(p, t0, min(G, R - t0), table)
+        pick(p, table)
+    out = torch.empty((R, sb), dtype=x.dtype, device=dev)
+    check(L.ha_qsel_finish(dt, sb, R, _ptr(key), _ptr(nan), _ptr(out), st), "ha_qsel_finish")
+    return out
+
+
+def _order_statistics_native(x: torch.Tensor, ranks, axis: int, allreduce, n_total: int):
+    L = lib()
+    if not x.is_contiguous():
+        x = x.contiguous()
+    shape = list(x.shape)
+    n = shape[axis]
+    outer = 1
+    for d in shape[:axis]:
+        outer *= d
+    inner = 1
+    for d in shape[axis + 1:]:
+        inner *= d
+    rest = tuple(shape[:axis] + shape[axis + 1:])
+    if inner != 1 and outer != 1:
+        x = x.movedim(axis, -1).contiguous()
+        outer, inner = outer * inner, 1
+    layout, S = (0, outer) if inner == 1 else (1, inner)
+    R, esize = len(ranks), x.element_size()
+    dt = 0 if x.dtype == torch.float32 else 1
+    if S == 0:
+        return torch.empty((R,) + rest, dtype=x.dtype, device=x.device)
+    if layout == 0 and allreduce is None and n <= L.ha_qsel_small_len(dt):
+        out = torch.empty((R, S), dtype=x.dtype, device=x.device)
+        ranks_t = torch.tensor(ranks, dtype=torch.int64, device=x.device)
+        check(L.ha_qsel_rows_small(_ptr(x), dt, S, n, n, _ptr(ranks_t), R, _ptr(out),
+                                   ctypes.c_void_p(stream_ptr(x.device))), "ha_qsel_rows_small")
+        return out.reshape((R,) + rest)
+    nb = 2048 if layout == 0 else 256
+    smax = max(1, (QSEL_MAX_TABLE_BYTES // 8) // (R * (nb + 64)))
+    outs = []
+    for s0 in range(0, S, smax):
+        sb = min(smax, S - s0)
+        ptr = x.data_ptr() + (s0 * n if layout == 0 else s0) * esize
+        outs.append(_qsel_block(ptr, x, layout, sb, n, n if layout == 0 else inner, ranks, allreduce, n_total))
+    out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+    return out.reshape((R,) + rest)
+
+
+def order_statistics(x: torch.Tensor, ranks, axis: Optional[int] = None, allreduce=None,
+                     n_total: Optional[int] = None) -> torch.Tensor:
+    """The order statistics ``ranks`` (ascending, distinct, zero-based) of every slice of ``x`` along
+    ``axis`` (None: of the flattened tensor): ``[len(ranks), ...]`` in ``x``'s type, the remaining
+    dimensions in order. A slice that holds a NaN yields NaN for every rank.
+
+    Device float32 / float64: exact MSD radix select on the bit-ordered keys (``csrc/quantile.hip``) -
+    a histogram pass per digit over data that never moves, the keys under the targets' prefixes
+    compacted after the first digit when they are at most a quarter of the slice; one host read per
+    call. Rows short enough for a wave's registers are selected in one launch. ``HEAT_QUANTILE_NATIVE=0``
+    and everything else: ``torch.sort`` plus ``index_select``.
+
+    ``allreduce(t, "sum")`` sums the device tensor ``t`` in place over the ranks of an array split
+    along ``axis`` (called once per digit pass on the packed int64 table); ``ranks`` then are global and
+    ``n_total`` is the global length. Every rank gets the same result."""
+    ranks = [int(r) for r in ranks]
+    if axis is None:
+        x, axis = x.reshape(-1), 0
+    axis = axis % x.dim()
+    n_total = x.shape[axis] if n_total is None else int(n_total)
+    if not ranks or any(b <= a for a, b in zip(ranks, ranks[1:])) or ranks[0] < 0 or ranks[-1] >= n_total:
+        raise ValueError("order_statistics: ranks must be ascending, distinct and inside [0, {})".format(n_total))
+    if _qsel_native(x, allreduce is not None):
+        maxr = lib().ha_qsel_max_targets()
+        parts = [_order_statistics_native(x, ranks[i:i + maxr], axis, allreduce, n_total)
+                 for i in range(0, len(ranks), maxr)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
+    if allreduce is not None:
+        raise ValueError("order_statistics: a split axis needs device float32 / float64 data")
+    idx = torch.tensor(ranks, dtype=torch.int64, device=x.device)
+    picked = torch.sort(x, dim=axis).values.index_select(axis, idx).movedim(axis, 0)
+    if x.is_floating_point():
+        picked = picked.masked_fill(torch.isnan(x).any(dim=axis).unsqueeze(0), float("nan"))
+    return picked
 
 
 # --------------------------------------------------------------------------------------------- cdist

@@ -68,6 +68,23 @@ int ha_med_fixup(const void* X, int dtype, int64_t n, int f, int64_t ldx, const 
                  const void* mm, const void* prefix, void* fx, void* stream);
 int ha_med_finish(int dtype, int k, int f, const void* mm, const void* prefix, const void* counts, const void* fx,
                   void* med, void* stream);
+int ha_qsel_max_targets();
+int ha_qsel_group();
+int ha_qsel_passes(int dtype, int layout);
+int ha_qsel_small_len(int dtype);
+int64_t ha_qsel_table_elems(int layout, int64_t slices, int R, int pass, int64_t cap);
+int ha_qsel_rows_small(const void* x, int dtype, int64_t nrows, int64_t len, int64_t ld, const void* ranks, int R,
+                       void* out, void* stream);
+int ha_qsel_rows_pass(const void* src, int dtype, int layout, int mode, int64_t slices, int64_t len, int64_t ld,
+                      int nchunks, int pass, int R, int t0, int tg, int append, const void* prefix, const void* live,
+                      void* table, int64_t table_elems, void* comp, void* ccnt, int64_t ccap, void* stream);
+int ha_qsel_cols_pass(const void* X, int dtype, int64_t n, int64_t ncols, int64_t ld, int nchunks, int pass, int R,
+                      int t0, int tg, int append, const void* prefix, const void* live, void* table,
+                      int64_t table_elems, void* comp, void* ccnt, int64_t ccap, void* stream);
+int ha_qsel_pick(int dtype, int layout, int64_t slices, int R, int pass, const void* ranks, const void* table,
+                 int64_t table_elems, void* prefix, void* rank, void* cnt, void* live, void* key, void* nan,
+                 void* record, void* stream);
+int ha_qsel_finish(int dtype, int64_t slices, int R, const void* key, const void* nan, void* out, void* stream);
 }
 
 static int fails = 0;
@@ -188,6 +205,61 @@ int main() {
   CHECK(ha_med_fixup(dummy, 0, 4, 4, 4, idummy, idummy, -2, dummy, dummy, dummy, nullptr) == BAD);
   CHECK(ha_med_finish(0, 2, 4, dummy, dummy, dummy, dummy, nullptr, nullptr) == BAD);
   CHECK(ha_med_finish(0, 0, 4, dummy, dummy, dummy, dummy, dummy, nullptr) == BAD);       // k <= 0
+  // order statistics: table sizes, pass counts, and what the launchers reject before any device work
+  const int maxr = ha_qsel_max_targets();
+  CHECK(maxr >= ha_qsel_group() && ha_qsel_group() >= 2);
+  CHECK(ha_qsel_passes(0, 0) == 3 && ha_qsel_passes(1, 0) == 6 && ha_qsel_passes(0, 1) == 4 && ha_qsel_passes(1, 1) == 8);
+  CHECK(ha_qsel_small_len(0) == 2 * ha_qsel_small_len(1) && ha_qsel_small_len(1) > 0);
+  for (int layout : {0, 1})
+    for (int64_t slices : {(int64_t)1, (int64_t)7, (int64_t)1000, (int64_t)1 << 20}) {
+      const int64_t nb = layout ? 256 : 2048;
+      CHECK(ha_qsel_table_elems(layout, slices, 3, 0, INT64_MAX) == slices * (nb + 1));
+      CHECK(ha_qsel_table_elems(layout, slices, 3, 2, INT64_MAX) == slices * 3 * (nb + 64));
+      CHECK(ha_qsel_table_elems(layout, slices, 3, 1, slices * 3 * (nb + 64) - 1) == -1);  // above the cap
+    }
+  CHECK(ha_qsel_table_elems(2, 4, 1, 0, cap) == -1 && ha_qsel_table_elems(0, 0, 1, 0, cap) == -1);
+  CHECK(ha_qsel_table_elems(0, 4, 0, 0, cap) == -1 && ha_qsel_table_elems(0, 4, maxr + 1, 1, cap) == -1);
+  CHECK(ha_qsel_table_elems(1, (int64_t)1 << 31, 1, 0, INT64_MAX) == -1);
+  long long ldummy[16] = {0};
+  CHECK(ha_qsel_rows_small(dummy, 0, 1, 16, 16, nullptr, 1, dummy, nullptr) == BAD);
+  CHECK(ha_qsel_rows_small(dummy, 2, 1, 16, 16, ldummy, 1, dummy, nullptr) == BAD);       // dtype
+  CHECK(ha_qsel_rows_small(dummy, 0, 2, 16, 8, ldummy, 1, dummy, nullptr) == BAD);        // ld < len
+  CHECK(ha_qsel_rows_small(dummy, 0, 0, 16, 16, ldummy, 1, dummy, nullptr) == OK);        // no rows
+  CHECK(ha_qsel_rows_small(dummy, 0, 1, ha_qsel_small_len(0) + 1, 1 << 20, ldummy, 1, dummy, nullptr) == UNSUP);
+  CHECK(ha_qsel_rows_small(dummy, 1, 1, 16, 16, ldummy, maxr + 1, dummy, nullptr) == UNSUP);
+  CHECK(ha_qsel_rows_pass(dummy, 0, 0, 0, 1, 16, 16, 1, 3, 1, 0, 1, 0, ldummy, idummy, ldummy, 4096, nullptr, nullptr, 0,
+                          nullptr) == BAD);  // float32 has 3 passes of 11 bits
+  CHECK(ha_qsel_rows_pass(dummy, 0, 0, 0, 1, 16, 16, 1, 1, 9, 0, 9, 0, ldummy, idummy, ldummy, 1 << 20, nullptr, nullptr,
+                          0, nullptr) == BAD);  // more targets than a launch takes
+  CHECK(ha_qsel_rows_pass(dummy, 0, 0, 0, 1, 16, 16, 1, 1, 2, 0, 2, 1, ldummy, idummy, ldummy, 1 << 20, nullptr, nullptr,
+                          0, nullptr) == BAD);  // append without a buffer
+  CHECK(ha_qsel_rows_pass(dummy, 0, 0, 1, 1, 16, 16, 1, 1, 2, 0, 2, 0, ldummy, idummy, ldummy, 1 << 20, dummy, ldummy,
+                          4, nullptr) == BAD);  // compacted keys exist from pass 2 on
+  CHECK(ha_qsel_rows_pass(dummy, 0, 0, 0, 1, 16, 16, 1, 1, 2, 0, 2, 0, nullptr, idummy, ldummy, 1 << 20, nullptr,
+                          nullptr, 0, nullptr) == BAD);  // pass 1 without prefixes
+  CHECK(ha_qsel_rows_pass(dummy, 0, 0, 0, 0, 16, 16, 1, 0, 1, 0, 1, 0, nullptr, nullptr, ldummy, 16, nullptr, nullptr, 0,
+                          nullptr) == OK);  // no slices
+  CHECK(ha_qsel_rows_pass(dummy, 0, 0, 0, 1, 16, 16, 1, 0, 1, 0, 1, 0, nullptr, nullptr, ldummy, 2048, nullptr, nullptr,
+                          0, nullptr) == UNSUP);  // table smaller than [1][2048] + 1
+  CHECK(ha_qsel_rows_pass(dummy, 0, 0, 0, 1, (int64_t)1 << 40, (int64_t)1 << 40, 1, 0, 1, 0, 1, 0, nullptr, nullptr,
+                          ldummy, 4096, nullptr, nullptr, 0, nullptr) == UNSUP);  // 2^40 elements in one chunk
+  CHECK(ha_qsel_cols_pass(dummy, 0, 4, 4, 2, 1, 0, 1, 0, 1, 0, nullptr, nullptr, ldummy, 4096, nullptr, nullptr, 0,
+                          nullptr) == BAD);  // ld < ncols
+  CHECK(ha_qsel_cols_pass(dummy, 0, 4, 4, 4, 1, 4, 1, 0, 1, 0, ldummy, idummy, ldummy, 4096, nullptr, nullptr, 0,
+                          nullptr) == BAD);  // float32 has 4 passes of 8 bits
+  CHECK(ha_qsel_cols_pass(dummy, 1, 4, 4, 4, 1, 0, 1, 0, 1, 0, nullptr, nullptr, ldummy, 4 * 257 - 1, nullptr, nullptr, 0,
+                          nullptr) == UNSUP);  // table smaller than [4][256] + 4
+  CHECK(ha_qsel_cols_pass(dummy, 1, 0, 4, 4, 1, 0, 1, 0, 1, 0, nullptr, nullptr, ldummy, 16, nullptr, nullptr, 0,
+                          nullptr) == OK);  // no rows
+  CHECK(ha_qsel_pick(0, 0, 1, 1, 0, nullptr, ldummy, 4096, ldummy, ldummy, ldummy, idummy, ldummy, ldummy, ldummy,
+                     nullptr) == BAD);
+  CHECK(ha_qsel_pick(0, 1, 1, 1, 0, ldummy, ldummy, 256, ldummy, ldummy, ldummy, idummy, ldummy, ldummy, ldummy,
+                     nullptr) == UNSUP);  // table smaller than [1][256] + 1
+  CHECK(ha_qsel_pick(1, 1, 1, 1, 8, ldummy, ldummy, 4096, ldummy, ldummy, ldummy, idummy, ldummy, ldummy, ldummy,
+                     nullptr) == BAD);  // float64 has 8 passes of 8 bits
+  CHECK(ha_qsel_finish(0, 4, 1, ldummy, ldummy, nullptr, nullptr) == BAD);
+  CHECK(ha_qsel_finish(0, 4, maxr + 1, ldummy, ldummy, dummy, nullptr) == BAD);
+  CHECK(ha_qsel_finish(1, 0, 1, ldummy, ldummy, dummy, nullptr) == OK);
   if (fails) {
     fprintf(stderr, "%d checks failed\n", fails);
     return 1;
